@@ -7,6 +7,10 @@ Metric (BASELINE.json): "tokens/sec GPT-3-13B sharding-3 + ResNet50 img/s, at 1/
 `value` = whole-job GPT-3 13B training tokens/s; ResNet-50 img/s is reported in `secondary`.
 Weak scaling: per-GPU micro-batch fixed as N grows. Data: synthetic tokens / images, random init.
 
+A plain run does what `value` needs: set-up, --warmup steps, --steps timed steps (`ms_per_step` each), the result
+line. `--full` adds the ResNet-50 half of the metric (`secondary`). `--dump-outputs DIR` writes what the last timed
+step computed (losses, a seeded sample of the updated parameters) as DIR/<name>.npy; same arguments, same inputs.
+
 Launch (N>1): python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
               --master-port P bench.py --gpus N --steps K --warmup W
 `python bench.py --gpus N` without a launcher starts those N ranks itself (a child torchrun, before any
@@ -80,6 +84,13 @@ def parse():
     p.add_argument("--skip-gpt", type=int, default=0)
     p.add_argument("--allocator", default="native", choices=["native", "torch"],
                    help="device allocator: the framework's auto-growth best-fit allocator or PyTorch's")
+    p.add_argument("--full", action="store_true",
+                   help="also run what the headline figure does not need: the ResNet-50 benchmark (`secondary`; "
+                        "--resnet / --resnet-* / --skip-gpt apply only here). A plain run sets up, warms up, times "
+                        "--steps steps of the language model and prints the result line")
+    p.add_argument("--dump-outputs", default=None, metavar="DIR",
+                   help="after the timed steps write what the last one computed as DIR/<name>.npy (float32): the "
+                        "micro-batch losses and a fixed, seeded sample of the updated parameters (rank 0's shards)")
     a = p.parse_args()
     mb, acc = (4, 4) if a.model == "gpt3-13b" else (2, 8)
     a.micro_batch = mb if a.micro_batch is None else a.micro_batch
@@ -121,6 +132,54 @@ def timed(step_fn, steps, warmup, dist_on):
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
     return dt
+
+
+OUTPUTS = {}  # --dump-outputs: name -> float32 numpy array of what the last timed step computed
+_DUMP_BUDGET = 6 << 20  # sampled elements per call of _sample_params (24 MB of float32)
+
+
+def _step_tensors(model):
+    """(name, tensor) of the state a training step updates: under the sharding engine this rank's flat
+    parameter shards (always resident, also at stage 3), otherwise the model's parameters."""
+    eng = getattr(model, "_engine", None)
+    if eng is not None and getattr(eng, "units", None):
+        return [(f"{u.name}.flat{j}", f.shard._t) for u in eng.units for j, f in enumerate(u.flats)]
+    return [(n, getattr(p, "_t", p)) for n, p in model.named_parameters()]
+
+
+@torch.no_grad()
+def _sample_params(model):
+    """Fixed, seeded sample of the updated parameters as one float32 vector: the same element indices of the same
+    tensors on every run with the same arguments (small tensors whole)."""
+    import numpy as np
+    tensors = [(n, t) for n, t in _step_tensors(model) if t.numel() > 0]
+    per = max(1, _DUMP_BUDGET // max(len(tensors), 1))
+    out = []
+    for i, (_, t) in enumerate(tensors):
+        flat = t.detach().reshape(-1)
+        if flat.numel() > per:
+            g = torch.Generator().manual_seed(20240 + i)
+            idx = torch.randint(0, flat.numel(), (per,), generator=g).sort().values
+            flat = flat[idx.to(flat.device)]
+        out.append(flat.float().cpu().numpy())
+    return np.concatenate(out) if out else np.zeros(0, dtype=np.float32)
+
+
+def _record_outputs(args, prefix, losses, model):
+    if not args.dump_outputs or int(os.environ.get("RANK", "0")) != 0:
+        return
+    import numpy as np
+    if losses is not None:
+        OUTPUTS[prefix + "loss"] = np.asarray([float(l) for l in losses], dtype=np.float32)
+    OUTPUTS[prefix + "params_sample"] = _sample_params(model)
+
+
+def _write_outputs(path):
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    for name, arr in OUTPUTS.items():
+        np.save(os.path.join(path, name + ".npy"), arr)
+    log(f"[dump] wrote {', '.join(f'{n}.npy{list(a.shape)}' for n, a in OUTPUTS.items())} to {path}")
 
 
 def gpt_bench(args, paddle, world, dist_on):
@@ -181,6 +240,7 @@ def gpt_bench(args, paddle, world, dist_on):
     from paddlepaddle_amd.ops import linear as LIN
 
     def step():
+        losses = state["losses"] = []
         for a in range(args.accum):
             # accumulation micro-batches skip the gradient reduce-scatter / all-reduce; the last one
             # reduces (overlapped with its backward)
@@ -199,11 +259,13 @@ def gpt_bench(args, paddle, world, dist_on):
                 if args.accum > 1:
                     loss = loss * (1.0 / args.accum)
                 loss.backward()
+                losses.append(loss.detach())  # a scalar view: no kernel, no graph kept alive
         opt.step()
         opt.clear_grad()
         state["loss"] = loss
 
     dt = timed(step, args.steps, args.warmup, dist_on)
+    _record_outputs(args, "", state.get("losses", []), model)
     tokens = args.steps * args.accum * B * S * n_shard
     tps = tokens / dt
     fpt = cfg.flops_per_token(S, recompute=False)
@@ -302,6 +364,7 @@ def llama_static_bench(args, paddle, world, dist_on):
         state["loss"] = dm(x, y)
 
     dt = timed(step, args.steps, args.warmup, dist_on)
+    _record_outputs(args, "", [state["loss"]] if "loss" in state else [], model)
     tokens = args.steps * gb * args.seq_len
     tps = tokens / dt
     mfu = tps * cfg.flops_per_token(args.seq_len) / (PEAK_BF16 * world)
@@ -370,6 +433,7 @@ def llama_bench(args, paddle, world, dist_on):
             state["loss"] = loss
 
     dt = timed(step, args.steps, args.warmup, dist_on)
+    _record_outputs(args, "", [state["loss"]] if "loss" in state else [], model)
     tokens = args.steps * gb * dp * args.seq_len
     tps = tokens / dt
     mfu = tps * cfg.flops_per_token(args.seq_len) / (PEAK_BF16 * world)
@@ -429,6 +493,7 @@ def resnet_bench(args, paddle, world, dist_on):
             log(f"[resnet50] hipGraph capture failed ({type(e).__name__}: {e}); timing eager steps")
             torch.cuda.synchronize()
     dt = timed(run, args.resnet_steps, max(args.warmup, 3), dist_on)
+    _record_outputs(args, "resnet50_", None, model)
     ips = args.resnet_steps * B * world / dt
     log(f"[resnet50] step={dt / args.resnet_steps * 1000:.1f}ms img/s={ips:.0f}" +
         (" (hipGraph replay of the whole step)" if resnet_bench.graph else ""))
@@ -473,6 +538,8 @@ def main():
     args = parse()
     if args.tp is None:
         args.tp = 2 if (args.gpus > 1 and args.gpus % 2 == 0 and not args.model.startswith("llama")) else 1
+    if args.skip_gpt and not args.full:
+        raise SystemExit("--skip-gpt 1 leaves only the ResNet-50 benchmark, which runs under --full")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         _relaunch(args)
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -494,7 +561,10 @@ def main():
         args.resnet = 0
     elif not args.skip_gpt:
         tps, step_ms, gb, mfu = gpt_bench(args, paddle, world, dist_on)
-    ips = resnet_bench(args, paddle, world, dist_on) if args.resnet else None
+    # the headline figure needs only the language model's steps: the ResNet-50 half of the metric runs under --full
+    ips = resnet_bench(args, paddle, world, dist_on) if (args.full and args.resnet) else None
+    if args.dump_outputs and int(os.environ.get("RANK", "0")) == 0:
+        _write_outputs(args.dump_outputs)
     if int(os.environ.get("RANK", "0")) == 0:
         ns = world // max(args.tp, 1)
         par = (f"sharding_stage{args.sharding_stage}_degree{ns}" if args.sharding_stage else f"dp{ns}") + \

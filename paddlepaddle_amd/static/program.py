@@ -214,7 +214,9 @@ class Program:
             self._consts.append(t)
             self._const_of[id(t)] = i
             prm = _PARAM_OF.get(id(t))
-            if prm is not None:
+            # ids are reused: a parameter of an earlier program that is still waiting for the garbage collector can
+            # sit under the id of a buffer it has since replaced, so the entry counts only if it still holds ``t``
+            if prm is not None and prm._t is t:
                 self._params[i] = prm  # the program owns its parameters (layers may be temporaries)
         return _Const(t, i)
 

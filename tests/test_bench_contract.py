@@ -22,7 +22,7 @@ def test_bench_two_ranks_json_line():
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
            "127.0.0.1", "--master-port", str(_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--tp", "1",
            "--model", "tiny", "--steps", "2", "--warmup", "1", "--seq-len", "64", "--micro-batch", "2", "--accum", "2",
-           "--resnet-batch", "2", "--resnet-steps", "1"]
+           "--full", "--resnet-batch", "2", "--resnet-steps", "1"]
     r = subprocess.run(cmd, env=env, capture_output=True, timeout=600, cwd="/tmp")
     assert r.returncode == 0, r.stderr.decode()[-3000:]
     lines = [l for l in r.stdout.decode().splitlines() if l.startswith("{")]
@@ -34,6 +34,41 @@ def test_bench_two_ranks_json_line():
     assert d["n_gpus"] == 2 and d["steps"] == 2 and d["value"] > 0 and d["dtype"] == "bf16"
     assert d["config"]["parallelism"] == "sharding_stage3_degree2"
     assert d["secondary"]["value"] > 0
+
+
+def test_bench_plain_run_is_lean_and_dumps_repeatable_outputs(tmp_path):
+    """A plain run times only the language model (no ResNet-50: that is --full), `--steps` is the number of timed
+    steps, and `--dump-outputs` writes the last step's losses and parameter sample as float32 .npy files that two
+    runs with the same arguments reproduce bit for bit."""
+    import numpy as np
+    env = dict(os.environ, PADDLE_AMD_FORCE_CPU="1", PYTHONPATH=ROOT, OMP_NUM_THREADS="2")
+    for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
+        env.pop(k, None)
+    got = []
+    for name in ("a", "b"):
+        out = tmp_path / name
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--model", "tiny", "--steps", "3",
+               "--warmup", "1", "--seq-len", "64", "--micro-batch", "2", "--accum", "2", "--dump-outputs", str(out)]
+        r = subprocess.run(cmd, env=env, capture_output=True, timeout=600, cwd=str(tmp_path))
+        assert r.returncode == 0, r.stderr.decode()[-3000:]
+        assert "[resnet50]" not in r.stderr.decode()
+        lines = [l for l in r.stdout.decode().splitlines() if l.startswith("{")]
+        assert len(lines) == 1
+        d = json.loads(lines[0])
+        assert d["steps"] == 3 and d["warmup"] == 1 and d["ms_per_step"] > 0 and d["value"] > 0
+        assert d["unit"] == "tokens/s" and d["higher_is_better"] is True and d["dtype"] == "bf16"
+        assert d["secondary"]["value"] is None
+        # tokens/s and ms_per_step describe the same 3 timed steps of 2 x 2 x 64 tokens
+        assert abs(d["value"] * d["ms_per_step"] / 1000 - 2 * 2 * 64) < 0.01 * 2 * 2 * 64
+        files = sorted(p.name for p in out.iterdir())
+        assert files == ["loss.npy", "params_sample.npy"]
+        arrs = {f: np.load(out / f) for f in files}
+        assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in arrs.values())
+        assert arrs["loss.npy"].shape == (2,) and arrs["params_sample.npy"].size > 1000
+        assert sum(a.nbytes for a in arrs.values()) <= 64 << 20
+        got.append(arrs)
+    for f in got[0]:
+        np.testing.assert_array_equal(got[0][f], got[1][f])
 
 
 def test_bench_llama_pipeline_x_tp_four_ranks():
