@@ -1,12 +1,14 @@
 """Dynamic loss scaling. Reference: python/paddle/amp/grad_scaler.py:62 AmpScaler, :657 GradScaler.
-The found-inf check and the unscale are fused into the multi-tensor path: grads are checked with
-one torch._amp_foreach_non_finite_check_and_unscale_ launch (device-side found_inf flag, no host
-sync until update())."""
+The found-inf check and the unscale are one multi-tensor pass over the gradients (ops/amp.py: one HIP launch
+for all dtypes on the GPU) with a device-side found_inf flag. Under sharding / tensor / pipeline parallelism the
+flag is max-reduced over the scaler's ``_found_inf_groups`` so every rank takes or skips the same step; the host
+reads it once per step, in step()."""
 from __future__ import annotations
 
 from enum import Enum
 
 import torch
+import torch.distributed as dist
 
 from ..framework.tensor import Tensor, _wrap
 
@@ -17,7 +19,28 @@ class OptimizerState(Enum):
     STEPPED = 2
 
 
+def add_found_inf_groups(scaler, groups):
+    """Add communication groups (``Group`` objects; None = the world group) over which ``scaler`` max-reduces its
+    found_inf flag. Groups of one rank and groups already present (same ranks) are left out."""
+    have = {ranks for ranks, _ in scaler._found_inf_groups}
+    out = list(scaler._found_inf_groups)
+    for g in groups:
+        if g is None:
+            if not (dist.is_available() and dist.is_initialized()):
+                continue
+            ranks, pg = tuple(range(dist.get_world_size())), None
+        else:
+            ranks, pg = tuple(g.ranks), g.process_group
+        if len(ranks) > 1 and ranks not in have:
+            have.add(ranks)
+            out.append((ranks, pg))
+    scaler._found_inf_groups = tuple(out)
+    return scaler
+
+
 class AmpScaler:
+    _found_inf_groups = ()  # ((ranks, process group), ...): orthogonal groups, reduced one after the other
+
     def __init__(self, enable=True, init_loss_scaling=2.0 ** 15, incr_ratio=2.0, decr_ratio=0.5,
                  incr_every_n_steps=1000, decr_every_n_nan_or_inf=1, use_dynamic_loss_scaling=True):
         self._enable = enable
@@ -28,6 +51,7 @@ class AmpScaler:
         self._incr_count = 0
         self._decr_count = 0
         self._found_inf = None
+        self._found_host = None  # (flag tensor, its host value): read once per step
         self._opt_states = {}
         self._scale_t = None
 
@@ -48,26 +72,46 @@ class AmpScaler:
             return var
         return _wrap(var._t * self._scale)
 
+    def _amp_grads_of(self, optimizer):
+        fn = getattr(optimizer, "_amp_grads", None)
+        if fn is not None:  # optimizers whose gradients do not hang off _parameter_list (sharding engine)
+            return [g for g in fn() if g is not None]
+        return [p._t.grad for p in optimizer._parameter_list if p._t.grad is not None]
+
+    def _sync_found_inf(self, found):
+        """MAX over every group in turn (orthogonal groups: the result is the global flag). Runs on ranks without
+        gradients too, so all members issue the same collectives."""
+        for _, pg in self._found_inf_groups:
+            want = "cpu" if dist.get_backend(pg) == "gloo" else "cuda"
+            if found.device.type != want:
+                found = found.cpu() if want == "cpu" else found.to(torch.device("cuda", torch.cuda.current_device()))
+            dist.all_reduce(found, op=dist.ReduceOp.MAX, group=pg)
+        return found
+
     def unscale_(self, optimizer):
         if not self._enable:
             return
         st = self._opt_states.get(id(optimizer), OptimizerState.INIT)
         if st == OptimizerState.UNSCALED:
             return
-        grads = [p._t.grad for p in optimizer._parameter_list if p._t.grad is not None]
+        grads = self._amp_grads_of(optimizer)
         if not grads:
-            self._found_inf = torch.zeros(1)
+            self._found_inf = self._sync_found_inf(torch.zeros(1))
             return
+        from ..ops.amp import check_finite_and_unscale_
         dev = grads[0].device
         found = torch.zeros(1, dtype=torch.float32, device=dev)
         inv = torch.full((1,), 1.0 / self._scale, dtype=torch.float32, device=dev)
-        by_dtype = {}
-        for g in grads:
-            by_dtype.setdefault((g.device, g.dtype), []).append(g)
-        for gs in by_dtype.values():
-            torch._amp_foreach_non_finite_check_and_unscale_(gs, found, inv)
-        self._found_inf = found
+        check_finite_and_unscale_(grads, inv, found)
+        self._found_inf = self._sync_found_inf(found)
         self._opt_states[id(optimizer)] = OptimizerState.UNSCALED
+
+    def _found(self):
+        """The step's found_inf as a host bool: one device read per flag tensor, kept until update()."""
+        src = self._found_inf
+        if self._found_host is None or self._found_host[0] is not src:
+            self._found_host = (src, src is not None and bool(src.item()))
+        return self._found_host[1]
 
     def minimize(self, optimizer, *args, **kwargs):
         self.step(optimizer)
@@ -79,7 +123,7 @@ class AmpScaler:
             optimizer.step()
             return
         self.unscale_(optimizer)
-        if self._found_inf is not None and bool(self._found_inf.item()):
+        if self._found():
             self._opt_states[id(optimizer)] = OptimizerState.STEPPED
             self._skip = True
             return
@@ -90,7 +134,7 @@ class AmpScaler:
     def update(self):
         if not self._enable:
             return
-        found = self._found_inf is not None and bool(self._found_inf.item())
+        found = self._found()  # read by step(); lazily here only when step() was not called
         if self._use_dynamic:
             if found:
                 self._incr_count = 0
@@ -106,6 +150,7 @@ class AmpScaler:
                     self._incr_count = 0
         self._opt_states = {}
         self._found_inf = None
+        self._found_host = None
 
     def state_dict(self):
         return {"scale": self._scale, "incr_ratio": self._incr_ratio, "decr_ratio": self._decr_ratio,

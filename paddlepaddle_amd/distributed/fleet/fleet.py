@@ -237,6 +237,15 @@ class _Fleet:
         return HybridParallelOptimizer(optimizer, self._hcg, self._strategy)
 
     def distributed_scaler(self, scaler):
+        """Reference fleet/scaler.py:27-147: found_inf is max-reduced over the mp, pp and sharding groups, so every
+        rank takes or skips the same step. Groups a GroupShardedScaler already added are kept (the sets unite)."""
+        hcg = self._hcg
+        if hcg is None:
+            return scaler
+        from ...amp.grad_scaler import add_found_inf_groups
+        groups = [g for g in (hcg.get_model_parallel_group(), hcg.get_pipe_parallel_group(),
+                              hcg.get_sharding_parallel_group()) if g is not None]
+        add_found_inf_groups(getattr(scaler, "_inner_scaler", scaler), groups)
         return scaler
 
     # ---------------------------------------------------------------- io

@@ -7,3 +7,4 @@ from ....parallel.tensor_parallel import (ColumnParallelLinear, RowParallelLinea
                                           ParallelCrossEntropy, get_rng_state_tracker, model_parallel_random_seed)
 from ..fleet import TensorParallel  # noqa: F401
 from ....parallel.sharding import GroupShardedModel as ShardingParallel  # noqa: F401
+from ....parallel.sharding import GroupShardedScaler  # noqa: F401

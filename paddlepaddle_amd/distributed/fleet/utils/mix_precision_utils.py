@@ -120,7 +120,7 @@ def _unscale_main_grads(self, optimizer):
         elif p._t.grad is not None:
             grads.append(p._t.grad)
     if not grads:
-        self._found_inf = torch.zeros(1)
+        self._found_inf = self._sync_found_inf(torch.zeros(1))
         return
     dev = grads[0].device
     found = torch.zeros(1, dtype=torch.float32, device=dev)
@@ -130,7 +130,7 @@ def _unscale_main_grads(self, optimizer):
         by.setdefault((g.device, g.dtype), []).append(g)
     for gs in by.values():
         torch._amp_foreach_non_finite_check_and_unscale_(gs, found, inv)
-    self._found_inf = found
+    self._found_inf = self._sync_found_inf(found)  # no-op unless the scaler was made distributed
     self._opt_states[id(optimizer)] = OptimizerState.UNSCALED
 
 

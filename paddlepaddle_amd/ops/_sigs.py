@@ -44,6 +44,8 @@ SIGS = {
     "pa_write_i64": [_vp, _vp, _i64, _vp],
     "pa_bn_set_target_wgs": [_i32],
     "pa_momentum_multi": [_vp, _vp, _i64, _vp, _f32, _f32, _f32, _i32, _vp],
+    # loss scaling (csrc/kernels/amp.hip)
+    "pa_amp_check_unscale_multi": [_vp, _vp, _i64, _vp, _vp, _vp],
     # attention
     "pa_flash_attn_fwd": [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _f32, _i32, _vp],
     "pa_flash_attn_bwd": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,

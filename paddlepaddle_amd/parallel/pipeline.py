@@ -311,7 +311,7 @@ class PipelineParallel(nn.Layer):
     def _backward_step(self, inp, out, mb=0):
         if self.is_last:
             self._flush()
-            (out._t / self.accumulate_steps).backward()
+            self._scaled_loss(out._t / self.accumulate_steps).backward()
         else:
             g = self._recv(self.next_rank, _BWD, (0, mb))
             out._t.backward(g)
@@ -358,11 +358,30 @@ class PipelineParallel(nn.Layer):
         from ..ops.linear import fuse_grad_accumulation
         self._mg_params = fuse_grad_accumulation(self._layers, getattr(self, "_mg_params", None))
 
+    _loss_scaler = None  # the enabled GradScaler of the running train_batch
+
+    def _scaled_loss(self, t):
+        """The last stage's micro-batch loss times the loss scale (the scaled gradient then travels upstream
+        through the p2p backward messages); the loss train_batch returns stays unscaled."""
+        return t if self._loss_scaler is None else self._loss_scaler.scale(_wrap(t))._t
+
     def train_batch(self, data, optimizer, lr_scheduler=None, scaler=None):
         self._layers.train()
         self._fuse_grad_accumulation()
-        loss = self.forward_backward_pipeline(data, scaler)
-        optimizer.step()
+        if scaler is not None and scaler.is_enable():
+            # stages hold disjoint layers: an overflow on one must skip the step on all of them
+            from ..amp.grad_scaler import add_found_inf_groups
+            add_found_inf_groups(getattr(scaler, "_inner_scaler", scaler), [self.group])
+            self._loss_scaler = scaler
+            try:
+                loss = self.forward_backward_pipeline(data, scaler)
+            finally:
+                self._loss_scaler = None
+            scaler.step(optimizer)
+            scaler.update()
+        else:
+            loss = self.forward_backward_pipeline(data, scaler)
+            optimizer.step()
         optimizer.clear_grad()
         if lr_scheduler is not None:
             lr_scheduler.step()
@@ -484,7 +503,7 @@ class PipelineParallelWithInterleave(PipelineParallel):
         x, out = store.pop((v, mb))
         if last:
             self._flush()
-            (out._t / self.accumulate_steps).backward()
+            self._scaled_loss(out._t / self.accumulate_steps).backward()
         else:
             # the gradient of chunk v's output comes from chunk v (or v+1 across the wrap) downstream
             src_v = v + 1 if self.stage_id == self.num_stages - 1 else v

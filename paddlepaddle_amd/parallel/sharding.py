@@ -475,6 +475,19 @@ class GroupShardedEngine:
         self._in_backward = False
 
     # ------------------------------------------------------------------ optimizer
+    def shard_grads(self):
+        """The gradient tensors this rank owns after a finalized backward, one per flat buffer: the flat gradient
+        buffer itself at degree 1, the fp32 reduce-scattered shard gradient above. step() hands exactly these to
+        the optimizer, so a loss scaler unscales (and checks) them in place before the step."""
+        if self.world == 1:
+            return [f.alloc_full_grad() for u in self.units for f in u.flats]
+        return [f.shard_grad for u in self.units for f in u.flats]
+
+    def comm_groups(self):
+        """Every group of more than one rank this engine communicates over (None = the world group)."""
+        out = [self.group] if self.world > 1 else []
+        return out + [g for g in (self.dp_group, self.mp_group, self.pp_group, self.sep_group) if g is not None]
+
     @torch.no_grad()
     def step(self):
         from ..distributed import collective_check as _cc
@@ -707,6 +720,10 @@ class GroupShardedOptimizer:
     def step(self):
         self._engine.step()
 
+    def _amp_grads(self):
+        """Gradients a GradScaler unscales for this optimizer (the shards' .grad is bound only inside step())."""
+        return self._engine.shard_grads()
+
     def clear_grad(self, set_to_zero=True):
         self._engine.clear_grad(set_to_zero)
 
@@ -732,6 +749,18 @@ class GroupShardedOptimizer:
         return getattr(self._inner, k)
 
 
+def GroupShardedScaler(scaler, engine):
+    """Make ``scaler`` work on a sharded optimizer (reference: group_sharded_utils.py GroupShardedScaler). Patches
+    the user's scaler object in place, as the reference does, so a reference they kept works too: its found_inf
+    flag is max-reduced over every multi-rank group of the engine (sharding, dp, mp, pp, sep), so all ranks skip
+    the step together (a rank stepping alone would issue all-gathers nobody joins). The gradients come from
+    GroupShardedOptimizer._amp_grads."""
+    from ..amp.grad_scaler import add_found_inf_groups
+    inner = getattr(scaler, "_inner_scaler", scaler)
+    add_found_inf_groups(inner, engine.comm_groups())
+    return scaler
+
+
 def group_sharded_parallel(model, optimizer, level, scaler=None, group=None, offload=False, sync_buffers=False,
                            buffer_max_size=2 ** 23, segment_size=2 ** 20, sync_comm=False, dp_group=None,
                            exclude_layer=None):
@@ -748,7 +777,8 @@ def group_sharded_parallel(model, optimizer, level, scaler=None, group=None, off
             group = hcg.get_sharding_parallel_group()
     eng = GroupShardedEngine(model, optimizer, stage, group, mp_group=mp_group, dp_group=dp_group,
                              offload=offload)
-    return GroupShardedModel(eng), GroupShardedOptimizer(eng), scaler
+    return (GroupShardedModel(eng), GroupShardedOptimizer(eng),
+            GroupShardedScaler(scaler, eng) if scaler is not None else None)
 
 
 def save_group_sharded_model(model, output, optimizer=None):

@@ -24,6 +24,7 @@ USER_FACING = {"amp.auto_cast", "distributed.fleet.recompute.recompute", "distri
                "distributed.fleet.meta_parallel.sharding.group_sharded_stage3",
                "distributed.fleet.meta_parallel.sharding.group_sharded_stage2",
                "distributed.fleet.meta_parallel.sharding.group_sharded_optimizer_stage2",
+               "distributed.fleet.meta_parallel.sharding.group_sharded_utils",
                "distributed.fleet.meta_parallel.pp_utils.utils", "distributed.fleet.utils.log_util",
                "distributed.fleet.meta_parallel.parallel_layers.random", "nn.functional.flash_attention"}
 
