@@ -29,8 +29,10 @@
 //   * epilogue: + bias[N], tanh-GELU (optionally storing the pre-activation for the backward),
 //     accumulate into an existing C (gradient-accumulation fusion), bf16 or fp32 output.
 #include "common.h"
+#include "gemm_plan.h"
+#include "launch.h"
 
-#include <climits>
+#include <type_traits>
 
 using namespace pa;
 
@@ -1422,26 +1424,29 @@ __global__ __launch_bounds__(kThreads, 1) void gemm3s_kernel(GemmArgs p0) {
   }
 }
 
-template <bool AK, bool BKM, bool CONV = false>
-int launch3s(const GemmArgs& a0, int splits, hipStream_t st) {
-  GemmArgs a = a0;
-  a.tiles_m = (a.M + kBM - 1) / kBM;
-  a.tiles_n = (a.N + kBN3 - 1) / kBN3;
-  const int smem = 3 * (kBM + kBN3) * kBK * 2;
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute((const void*)gemm3s_kernel<AK, BKM, CONV>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                              smem);
-    attr_set = true;
-  }
-  hipLaunchKernelGGL((gemm3s_kernel<AK, BKM, CONV>), dim3(a.tiles_m * a.tiles_n, splits), dim3(kThreads), smem, st,
-                     a);
-  return (int)hipGetLastError();
+// ---------------------------------------------------------------------------------------------
+// Host launchers. Every kernel with opt-in LDS goes through launch_lds (launch.h).
+
+// The two runtime operand-layout flags as compile-time booleans: f(bool_constant<AK>, bool_constant<BKM>).
+template <class F>
+int with_layout(int a_kmajor, int b_kmajor, F&& f) {
+  if (a_kmajor && !b_kmajor) return f(std::true_type{}, std::false_type{});
+  if (a_kmajor && b_kmajor) return f(std::true_type{}, std::true_type{});
+  if (!a_kmajor && !b_kmajor) return f(std::false_type{}, std::false_type{});
+  return f(std::false_type{}, std::true_type{});
 }
 
+template <bool AK, bool BKM, bool CONV = false>
+int launch3s(GemmArgs a, int splits, hipStream_t st) {
+  a.tiles_m = (a.M + kBM - 1) / kBM;
+  a.tiles_n = (a.N + kBN3 - 1) / kBN3;
+  constexpr int smem = 3 * (kBM + kBN3) * kBK * 2;
+  return launch_lds<gemm3s_kernel<AK, BKM, CONV>>(dim3(a.tiles_m * a.tiles_n, splits), dim3(kThreads), smem, st, a);
+}
+
+// grid == 0: one workgroup per tile, no tail
 template <bool AK, bool BKM, int SEG>
-int launch256_seg(const GemmArgs& a0, int splits, hipStream_t st, int grid) {
-  GemmArgs a = a0;
+int launch256_seg(GemmArgs a, int splits, hipStream_t st, int grid) {
   a.tiles_m = (a.M + 255) / 256;
   a.tiles_n = (a.N + 255) / 256;
   if (!grid) {
@@ -1450,15 +1455,8 @@ int launch256_seg(const GemmArgs& a0, int splits, hipStream_t st, int grid) {
   }
   constexpr int kLoop = 2 * 4 * 128 * kBK * 2, kEpi0 = 128 * kEpiRowStride * 4, kEpi1 = 256 * kEpiRowStrideBf16 * 2;
   constexpr int kEpi = kEpi0 > kEpi1 ? kEpi0 : kEpi1;
-  const int smem = kLoop > kEpi ? kLoop : kEpi;
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute((const void*)gemm256_kernel<AK, BKM, SEG>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                              smem);
-    attr_set = true;
-  }
-  hipLaunchKernelGGL((gemm256_kernel<AK, BKM, SEG>), dim3(grid, splits), dim3(kThreads), smem, st, a);
-  return (int)hipGetLastError();
+  constexpr int smem = kLoop > kEpi ? kLoop : kEpi;
+  return launch_lds<gemm256_kernel<AK, BKM, SEG>>(dim3(grid, splits), dim3(kThreads), smem, st, a);
 }
 
 template <bool AK, bool BKM>
@@ -1468,6 +1466,15 @@ int launch256(const GemmArgs& a0, int splits, hipStream_t st, int grid = 0, int 
   return launch256_seg<AK, BKM, 0>(a0, splits, st, grid);
 }
 
+template <bool AK, bool BKM>
+int launch4w(const GemmArgs& g, int grid, hipStream_t st) {
+  constexpr int kLoop = 4 * 2 * 256 * 32 * 2, kEpi = 128 * kEpiRowStride * 4;
+  constexpr int smem = kLoop > kEpi ? kLoop : kEpi;
+  return launch_lds<gemm4w_kernel<AK, BKM>>(dim3(grid), dim3(256), smem, st, g);
+}
+
+// BN: tile code of pa_gemm_bf16. The codes 0 and 160 return early without `else`, so the two-stage kernel below is
+// instantiated for them as well (BNk 256 and 160); the set of compiled kernels depends on it.
 template <int BN, bool AK, bool BKM>
 int launch(const GemmArgs& a0, int splits, hipStream_t st) {
   if constexpr (BN == 0) return launch256<AK, BKM>(a0, splits, st);
@@ -1477,24 +1484,22 @@ int launch(const GemmArgs& a0, int splits, hipStream_t st) {
   constexpr int BNk = (BN == 0 || BN == 4) ? 256 : BN;
   a.tiles_m = (a.M + kBM - 1) / kBM;
   a.tiles_n = (a.N + BNk - 1) / BNk;
-  const int smem = 2 * (kBM + BNk) * kBK * 2;
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute((const void*)gemm_bf16_kernel<BNk, AK, BKM, NW>,
-                              hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-    attr_set = true;
-  }
-  hipLaunchKernelGGL((gemm_bf16_kernel<BNk, AK, BKM, NW>), dim3(a.tiles_m * a.tiles_n, splits), dim3(NW * 64), smem,
-                     st, a);
-  return (int)hipGetLastError();
+  constexpr int smem = 2 * (kBM + BNk) * kBK * 2;
+  return launch_lds<gemm_bf16_kernel<BNk, AK, BKM, NW>>(dim3(a.tiles_m * a.tiles_n, splits), dim3(NW * 64), smem, st,
+                                                        a);
 }
 
-template <int BN>
-int dispatch_layout(const GemmArgs& a, int a_kmajor, int b_kmajor, int splits, hipStream_t st) {
-  if (a_kmajor && !b_kmajor) return launch<BN, true, false>(a, splits, st);
-  if (a_kmajor && b_kmajor) return launch<BN, true, true>(a, splits, st);
-  if (!a_kmajor && !b_kmajor) return launch<BN, false, false>(a, splits, st);
-  return launch<BN, false, true>(a, splits, st);
+// bn: 160 = three-stage 256x160 kernel; 256 (default) / 128 = two-stage kernel with 256x256 / 256x128 tiles;
+// 4 = two-stage 256x256 with 4 waves; 1 = 4-phase ping-pong 256x256 kernel
+int launch_bn(const GemmArgs& g, int bn, int a_kmajor, int b_kmajor, int splits, hipStream_t st) {
+  return with_layout(a_kmajor, b_kmajor, [&](auto ak, auto bk) {
+    constexpr bool AK = decltype(ak)::value, BKM = decltype(bk)::value;
+    if (bn == 160) return launch<160, AK, BKM>(g, splits, st);
+    if (bn == 128) return launch<128, AK, BKM>(g, splits, st);
+    if (bn == 1) return launch<0, AK, BKM>(g, splits, st);
+    if (bn == 4) return launch<4, AK, BKM>(g, splits, st);
+    return launch<256, AK, BKM>(g, splits, st);
+  });
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1669,109 +1674,82 @@ __global__ __launch_bounds__(256) void gemm_tail_reduce_k(GemmArgs p) {
   }
 }
 
-int device_cus() {
-  static int cus = 0;
-  if (!cus) {
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
-  }
-  return cus;
+// GemmArgs of the common operands; false when they break a requirement of the tile kernels (gemm_operands_ok, which
+// also holds the range check that makes the narrowing to int safe).
+bool gemm_args(GemmArgs& g, const void* a, const void* b, void* c, const void* bias, void* aux, int64_t M, int64_t N,
+               int64_t K, int64_t lda, int64_t ldb, int64_t ldc, int a_kmajor, int flags, float alpha) {
+  if (!gemm_operands_ok(M, N, K, kBK, lda, ldb, ldc, a_kmajor != 0)) return false;
+  g = GemmArgs{};
+  g.a = (const uint16_t*)a; g.b = (const uint16_t*)b; g.c = c;
+  g.bias = (const uint16_t*)bias; g.aux = (uint16_t*)aux;
+  g.lda = lda; g.ldb = ldb; g.ldc = ldc;
+  g.M = (int)M; g.N = (int)N; g.K = (int)K;
+  g.flags = flags; g.alpha = alpha;
+  return true;
 }
 
-// Tail plan of the ping-pong kernel: tiles beyond the last whole wave are split along K so the last wave
-// has about one workgroup per CU. Only when the remainder covers at most half the chip and every slice
-// keeps at least 4 K-tiles.
-void pp_plan(int64_t M, int64_t N, int64_t K, int cus, int* full, int* split) {
-  const int64_t T = ((M + 255) / 256) * ((N + 255) / 256);
-  const int64_t nk = K / kBK;
-  *full = (int)T;
-  *split = 0;
-  if (T <= cus) return;
-  const int64_t r = T % cus;
-  if (r == 0 || 2 * r > cus) return;
-  int sp = 1;
-  while (r * sp * 2 <= cus && nk % (sp * 2) == 0 && nk / (sp * 2) >= 4) sp *= 2;
-  if (sp == 1) return;
-  *full = (int)(T - r);
-  *split = sp;
+// Implicit-GEMM geometry (2-D callers: D = Do = 1, pad_d = 0); zero: >= 128 zeroed bytes read by padding taps.
+void set_conv_geometry(GemmArgs& g, const void* zero, int D, int H, int W, int C, int Do, int Ho, int Wo, int KH,
+                       int KW, int stride, int pad_d, int pad_h, int pad_w, int dil) {
+  g.zero = (const uint16_t*)zero;
+  g.cD = D; g.cDo = Do; g.cKHW = KH * KW; g.cPadD = pad_d;
+  g.cH = H; g.cW = W; g.cC = C; g.cHo = Ho; g.cWo = Wo; g.cKW = KW; g.cStride = stride; g.cPadH = pad_h;
+  g.cPadW = pad_w; g.cDil = dil;
+}
+
+// One 256x256-tile GEMM of checked operands g on kernel `kern` (1: 8-wave ping-pong, with operand segments `seg` as
+// launch256; 2: 4-wave K32 ring). force_split == 0: the balanced tail of tail_plan when ws is given
+// (pa_gemm_pp_ws_bytes bytes); otherwise every tile is cut into force_split K slices (ws:
+// pa_gemm_pp_splitk_ws_bytes). The plan that sized ws is the plan that is launched.
+int run_tile256(int kern, GemmArgs g, int a_kmajor, int b_kmajor, void* ws, hipStream_t st, int seg = 0,
+                int force_split = 0) {
+  if (g.M <= 0 || g.N <= 0 || g.K <= 0) return 0;
+  TailPlan pl = force_split ? split_all_plan(g.M, g.N, force_split) : tail_plan(g.M, g.N, g.K, kBK, device_cus());
+  if (!ws) pl = without_tail(pl);
+  if (!force_split) g.c_split = (int64_t)g.M * g.ldc;
+  g.tiles_m = (g.M + 255) / 256;
+  g.tiles_n = (g.N + 255) / 256;
+  g.full_tiles = pl.full_tiles;
+  g.tail_split = pl.split;
+  g.tail_ws = (float*)ws;
+  const int rc = with_layout(a_kmajor, b_kmajor, [&](auto ak, auto bk) {
+    constexpr bool AK = decltype(ak)::value, BKM = decltype(bk)::value;
+    return kern == 2 ? launch4w<AK, BKM>(g, pl.grid, st) : launch256<AK, BKM>(g, 1, st, pl.grid, seg);
+  });
+  if (rc || !pl.split) return rc;
+  hipLaunchKernelGGL(gemm_tail_reduce_k, dim3(pl.tiles - pl.full_tiles, 64), dim3(256), 0, st, g);
+  return (int)hipGetLastError();
+}
+
+// GemmArgs of an implicit-GEMM convolution forward (launch3s<true, true, true>; 2-D: D = KD = Do = 1, pad_d = 0):
+// out[N*Do*Ho*Wo, Cout] = im2col(x) . W^T (+ bias), every 64-deep K tile one filter tap. false: unsupported sizes.
+bool conv_fwd_args(GemmArgs& g, const void* x, const void* w, const void* bias, void* out, const void* zero, int N,
+                   int D, int H, int W, int C, int Cout, int KD, int KH, int KW, int stride, int pad_d, int pad_h,
+                   int pad_w, int dil, int Do, int Ho, int Wo, int flags) {
+  if (C % kBK != 0 || Cout % 8 != 0 || N <= 0) return false;
+  const int64_t K = (int64_t)KD * KH * KW * C;
+  if (!gemm_args(g, x, w, out, bias, nullptr, (int64_t)N * Do * Ho * Wo, Cout, K, C, K, Cout, 1,
+                 flags | (bias ? kEpiBias : 0), 1.f))
+    return false;
+  set_conv_geometry(g, zero, D, H, W, C, Do, Ho, Wo, KH, KW, stride, pad_d, pad_h, pad_w, dil);
+  return true;
 }
 
 }  // namespace
 
 // Workspace (bytes) the ping-pong GEMM needs for its balanced tail (0: none).
 PA_EXPORT int64_t pa_gemm_pp_ws_bytes(int64_t M, int64_t N, int64_t K) {
-  int full, split;
-  pp_plan(M, N, K, device_cus(), &full, &split);
-  if (!split) return 0;
-  const int64_t T = ((M + 255) / 256) * ((N + 255) / 256);
-  return (T - full) * split * 65536 * 4;
+  return tail_plan(M, N, K, kBK, device_cus()).ws_bytes;
 }
-
-namespace {
-template <bool AK, bool BKM>
-int launch4w(const GemmArgs& g, int grid, hipStream_t st) {
-  constexpr int kLoop = 4 * 2 * 256 * 32 * 2, kEpi = 128 * kEpiRowStride * 4;
-  constexpr int smem = kLoop > kEpi ? kLoop : kEpi;
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute((const void*)gemm4w_kernel<AK, BKM>, hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-    attr_set = true;
-  }
-  hipLaunchKernelGGL((gemm4w_kernel<AK, BKM>), dim3(grid), dim3(256), smem, st, g);
-  return (int)hipGetLastError();
-}
-
-// One 256x256-tile GEMM on kernel `kern` (1 8-wave ping-pong, 2 4-wave K32 ring) with the balanced tail when ws is given (pp_plan); g holds operands, sizes and epilogue fields.
-int run_tile256(int kern, GemmArgs g, int a_kmajor, int b_kmajor, void* ws, hipStream_t st) {
-  const int64_t M = g.M, N = g.N, K = g.K;
-  if (K % kBK != 0 || N % 8 != 0 || g.lda % 8 != 0 || g.ldb % 8 != 0 || g.ldc % 4 != 0) return 1;
-  if (!a_kmajor && M % 8 != 0) return 1;
-  if (M <= 0 || N <= 0 || K <= 0) return 0;
-  g.c_split = M * g.ldc;
-  int full, split;
-  pp_plan(M, N, K, device_cus(), &full, &split);
-  if (split && !ws) split = 0;
-  g.tiles_m = (int)((M + 255) / 256);
-  g.tiles_n = (int)((N + 255) / 256);
-  const int T = g.tiles_m * g.tiles_n;
-  g.full_tiles = split ? full : T;
-  g.tail_split = split;
-  g.tail_ws = (float*)ws;
-  const int grid = split ? full + (T - full) * split : T;
-  const int lay = (a_kmajor ? 0 : 2) + (b_kmajor ? 1 : 0);
-  int rc;
-  if (kern == 1) {
-    rc = lay == 0 ? launch256<true, false>(g, 1, st, grid) : lay == 1 ? launch256<true, true>(g, 1, st, grid)
-       : lay == 2 ? launch256<false, false>(g, 1, st, grid) : launch256<false, true>(g, 1, st, grid);
-  } else {
-    rc = lay == 0 ? launch4w<true, false>(g, grid, st) : lay == 1 ? launch4w<true, true>(g, grid, st)
-       : lay == 2 ? launch4w<false, false>(g, grid, st) : launch4w<false, true>(g, grid, st);
-  }
-  if (rc || !split) return rc;
-  hipLaunchKernelGGL(gemm_tail_reduce_k, dim3(T - full, 64), dim3(256), 0, st, g);
-  return (int)hipGetLastError();
-}
-
-GemmArgs tile256_args(const void* a, const void* b, void* c, const void* bias, void* aux, int64_t M, int64_t N,
-                      int64_t K, int64_t lda, int64_t ldb, int64_t ldc, int flags, float alpha) {
-  GemmArgs g{};
-  g.a = (const uint16_t*)a; g.b = (const uint16_t*)b; g.c = c;
-  g.bias = (const uint16_t*)bias; g.aux = (uint16_t*)aux;
-  g.lda = lda; g.ldb = ldb; g.ldc = ldc;
-  g.M = (int)M; g.N = (int)N; g.K = (int)K;
-  g.flags = flags; g.alpha = alpha;
-  return g;
-}
-}  // namespace
 
 // Ping-pong 256x256 GEMM (same operands / flags as pa_gemm_bf16, no split-K) with the balanced tail;
 // ws: pa_gemm_pp_ws_bytes(M, N, K) bytes (may be null when that is 0).
 PA_EXPORT int pa_gemm_bf16_pp(const void* a, const void* b, void* c, const void* bias, void* aux, int64_t M, int64_t N,
                               int64_t K, int64_t lda, int64_t ldb, int64_t ldc, int a_kmajor, int b_kmajor, int flags,
                               float alpha, void* ws, hipStream_t st) {
-  return run_tile256(1, tile256_args(a, b, c, bias, aux, M, N, K, lda, ldb, ldc, flags, alpha), a_kmajor, b_kmajor,
-                     ws, st);
+  GemmArgs g;
+  if (!gemm_args(g, a, b, c, bias, aux, M, N, K, lda, ldb, ldc, a_kmajor, flags, alpha)) return 1;
+  return run_tile256(1, g, a_kmajor, b_kmajor, ws, st);
 }
 
 // Split-K on the ping-pong kernel: every tile cut into `splits` K slices (the balanced-tail machinery with no
@@ -1779,36 +1757,16 @@ PA_EXPORT int pa_gemm_bf16_pp(const void* a, const void* b, void* c, const void*
 // gemm_tail_reduce_k — for products with few output tiles and a long K (the weight gradients of convolutions over
 // all pixels of a batch). Requires (K / 64) % splits == 0.
 PA_EXPORT int64_t pa_gemm_pp_splitk_ws_bytes(int64_t M, int64_t N, int splits) {
-  return ((M + 255) / 256) * ((N + 255) / 256) * (int64_t)splits * 65536 * 4;
+  return split_all_plan(M, N, splits).ws_bytes;
 }
 
 PA_EXPORT int pa_gemm_bf16_pp_splitk(const void* a, const void* b, void* c, int64_t M, int64_t N, int64_t K,
                                      int64_t lda, int64_t ldb, int64_t ldc, int a_kmajor, int b_kmajor, int flags,
                                      float alpha, int splits, void* ws, hipStream_t st) {
-  if (K % kBK != 0 || N % 8 != 0 || lda % 8 != 0 || ldb % 8 != 0 || ldc % 4 != 0 || splits < 1) return 1;
-  if ((K / kBK) % splits != 0 || !ws || (flags & ~(kEpiOutF32 | kEpiAccum))) return 1;
-  if (!a_kmajor && M % 8 != 0) return 1;
-  if (M <= 0 || N <= 0 || K <= 0) return 0;
-  GemmArgs g{};
-  g.a = (const uint16_t*)a; g.b = (const uint16_t*)b; g.c = c;
-  g.lda = lda; g.ldb = ldb; g.ldc = ldc;
-  g.M = (int)M; g.N = (int)N; g.K = (int)K;
-  g.flags = flags; g.alpha = alpha;
-  g.tiles_m = (int)((M + 255) / 256);
-  g.tiles_n = (int)((N + 255) / 256);
-  const int T = g.tiles_m * g.tiles_n;
-  g.full_tiles = 0;
-  g.tail_split = splits;
-  g.tail_ws = (float*)ws;
-  const int grid = T * splits;
-  int rc;
-  if (a_kmajor && !b_kmajor) rc = launch256<true, false>(g, 1, st, grid);
-  else if (a_kmajor && b_kmajor) rc = launch256<true, true>(g, 1, st, grid);
-  else if (!a_kmajor && !b_kmajor) rc = launch256<false, false>(g, 1, st, grid);
-  else rc = launch256<false, true>(g, 1, st, grid);
-  if (rc) return rc;
-  hipLaunchKernelGGL(gemm_tail_reduce_k, dim3(T, 64), dim3(256), 0, st, g);
-  return (int)hipGetLastError();
+  if (splits < 1 || (K / kBK) % splits != 0 || !ws || (flags & ~(kEpiOutF32 | kEpiAccum))) return 1;
+  GemmArgs g;
+  if (!gemm_args(g, a, b, c, nullptr, nullptr, M, N, K, lda, ldb, ldc, a_kmajor, flags, alpha)) return 1;
+  return run_tile256(1, g, a_kmajor, b_kmajor, ws, st, 0, splits);
 }
 
 // Segmented operands on the ping-pong kernel (GemmArgs::nseg): seg = [nseg][5] int64 host array of
@@ -1819,13 +1777,13 @@ PA_EXPORT int pa_gemm_bf16_pp_segs(const int64_t* seg, int nseg, int seg_k, cons
                                    const void* bias, int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldb,
                                    int64_t ldc, int a_kmajor, int b_kmajor, int flags, float alpha, void* ws,
                                    hipStream_t st) {
-  if (nseg < 1 || nseg > 4 || K % kBK != 0 || N % 8 != 0 || ldc % 4 != 0) return 1;
-  if (!a_kmajor && M % 8 != 0) return 1;
-  if (flags & (kEpiAux | kEpiStats)) return 1;
+  if (nseg < 1 || nseg > 4 || (flags & (kEpiAux | kEpiStats))) return 1;
+  // the leading dimensions of segmented operands come from the table (checked below); lda counts only for seg_k = 0
+  GemmArgs g;
+  if (!gemm_args(g, a, b, c, bias, nullptr, M, N, K, 0, 0, ldc, a_kmajor, flags, alpha)) return 1;
   if (M <= 0 || N <= 0) return 0;
-  GemmArgs g{};
-  g.a = (const uint16_t*)a; g.b = (const uint16_t*)b; g.c = c; g.bias = (const uint16_t*)bias;
-  g.lda = lda; g.ldb = ldb; g.ldc = ldc;
+  if (seg_k ? (flags & kEpiBias) != 0 : lda % 8 != 0) return 1;
+  g.lda = lda; g.ldb = ldb;
   g.nseg = nseg; g.seg_k = seg_k;
   int64_t prev = 0;
   for (int s = 0; s < 4; ++s) {
@@ -1845,38 +1803,16 @@ PA_EXPORT int pa_gemm_bf16_pp_segs(const int64_t* seg, int nseg, int seg_k, cons
     }
   }
   if (seg_k ? prev != K : prev != N) return 1;
-  if (!seg_k && (lda % 8 != 0)) return 1;
-  if (seg_k && (flags & kEpiBias)) return 1;
-  g.M = (int)M; g.N = (int)N; g.K = (int)K;
-  g.flags = flags; g.alpha = alpha;
-  g.c_split = M * ldc;
-  int full, split;
-  pp_plan(M, N, K, device_cus(), &full, &split);
-  if (split && !ws) split = 0;
-  g.tiles_m = (int)((M + 255) / 256);
-  g.tiles_n = (int)((N + 255) / 256);
-  const int T = g.tiles_m * g.tiles_n;
-  g.full_tiles = split ? full : T;
-  g.tail_split = split;
-  g.tail_ws = (float*)ws;
-  const int grid = split ? full + (T - full) * split : T;
-  int rc;
-  const int sg = nseg > 1 ? (seg_k ? 1 : 2) : 0;
-  if (a_kmajor && !b_kmajor) rc = launch256<true, false>(g, 1, st, grid, sg);
-  else if (a_kmajor && b_kmajor) rc = launch256<true, true>(g, 1, st, grid, sg);
-  else if (!a_kmajor && !b_kmajor) rc = launch256<false, false>(g, 1, st, grid, sg);
-  else rc = launch256<false, true>(g, 1, st, grid, sg);
-  if (rc || !split) return rc;
-  hipLaunchKernelGGL(gemm_tail_reduce_k, dim3(T - full, 64), dim3(256), 0, st, g);
-  return (int)hipGetLastError();
+  return run_tile256(1, g, a_kmajor, b_kmajor, ws, st, nseg > 1 ? (seg_k ? 1 : 2) : 0);
 }
 
 // 4-wave 256x256 GEMM (gemm4w_kernel; same operands / flags / workspace as pa_gemm_bf16_pp).
 PA_EXPORT int pa_gemm_bf16_4w(const void* a, const void* b, void* c, const void* bias, void* aux, int64_t M, int64_t N,
                               int64_t K, int64_t lda, int64_t ldb, int64_t ldc, int a_kmajor, int b_kmajor, int flags,
                               float alpha, void* ws, hipStream_t st) {
-  return run_tile256(2, tile256_args(a, b, c, bias, aux, M, N, K, lda, ldb, ldc, flags, alpha), a_kmajor, b_kmajor,
-                     ws, st);
+  GemmArgs g;
+  if (!gemm_args(g, a, b, c, bias, aux, M, N, K, lda, ldb, ldc, a_kmajor, flags, alpha)) return 1;
+  return run_tile256(2, g, a_kmajor, b_kmajor, ws, st);
 }
 
 // Output projection with the residual add in its epilogue: C = a . b (+ bias) + res (bf16, [M][ldc]; may not alias
@@ -1887,7 +1823,9 @@ PA_EXPORT int pa_gemm_bf16_res(const void* a, const void* b, void* c, const void
                                int64_t N, int64_t K, int64_t lda, int64_t ldb, int64_t ldc, int a_kmajor, int b_kmajor,
                                void* ws, hipStream_t st) {
   if (!res || res == c) return 1;
-  GemmArgs g = tile256_args(a, b, c, bias, nullptr, M, N, K, lda, ldb, ldc, (bias ? kEpiBias : 0) | kEpiResid, 1.f);
+  GemmArgs g;
+  if (!gemm_args(g, a, b, c, bias, nullptr, M, N, K, lda, ldb, ldc, a_kmajor, (bias ? kEpiBias : 0) | kEpiResid, 1.f))
+    return 1;
   g.res = (const uint16_t*)res;
   return run_tile256(1, g, a_kmajor, b_kmajor, ws, st);
 }
@@ -1901,8 +1839,10 @@ PA_EXPORT int pa_gemm_bf16_dgelu(const void* a, const void* b, void* dh, const v
                                  int64_t N, int64_t K, int64_t lda, int64_t ldb, int64_t ldc, int a_kmajor,
                                  int b_kmajor, int kern, hipStream_t st) {
   if (!pre || !colsum || kern < 1 || kern > 2) return 1;
-  GemmArgs g = tile256_args(a, b, dh, nullptr, const_cast<void*>(pre), M, N, K, lda, ldb, ldc,
-                            kEpiGeluBwd | kEpiColSum, 1.f);
+  GemmArgs g;
+  if (!gemm_args(g, a, b, dh, nullptr, const_cast<void*>(pre), M, N, K, lda, ldb, ldc, a_kmajor,
+                 kEpiGeluBwd | kEpiColSum, 1.f))
+    return 1;
   g.stats = colsum;
   return run_tile256(kern, g, a_kmajor, b_kmajor, nullptr, st);
 }
@@ -1910,35 +1850,22 @@ PA_EXPORT int pa_gemm_bf16_dgelu(const void* a, const void* b, void* dh, const v
 // Diagnostic ablations of gemm4w_kernel (A K-major, B MN-major, no tail): timing only.
 PA_EXPORT int pa_gemm_bf16_4w_abl(const void* a, const void* b, void* c, int64_t M, int64_t N, int64_t K, int abl,
                                   hipStream_t st) {
-  if (K % kBK || N % 256 || M % 256) return 1;
-  GemmArgs g{};
-  g.a = (const uint16_t*)a; g.b = (const uint16_t*)b; g.c = c;
-  g.lda = K; g.ldb = N; g.ldc = N; g.M = (int)M; g.N = (int)N; g.K = (int)K; g.alpha = 1.f;
+  GemmArgs g;
+  if (N % 256 || M % 256 || !gemm_args(g, a, b, c, nullptr, nullptr, M, N, K, K, N, N, 1, 0, 1.f)) return 1;
   g.tiles_m = (int)(M / 256); g.tiles_n = (int)(N / 256);
   g.full_tiles = g.tiles_m * g.tiles_n;
-  constexpr int smem = 128 * kEpiRowStride * 4;
-#define PA_G4A(V)                                                                                              \
-  do {                                                                                                         \
-    (void)hipFuncSetAttribute((const void*)gemm4w_kernel<true, false, V>,                                      \
-                              hipFuncAttributeMaxDynamicSharedMemorySize, smem);                               \
-    hipLaunchKernelGGL((gemm4w_kernel<true, false, V>), dim3(g.full_tiles), dim3(256), smem, st, g);           \
-  } while (0)
-  if (abl == 1) PA_G4A(1);
-  else if (abl == 2) PA_G4A(2);
-  else if (abl == 3) PA_G4A(3);
-  else if (abl == 5) PA_G4A(5);
-  else if (abl >= 6 && abl <= 8) {  // operand footprint ablations: 6 both, 7 B, 8 A read from one L2-resident row
+  if (abl >= 6 && abl <= 8) {  // operand footprint ablations: 6 both, 7 B, 8 A read from one L2-resident row
     if (abl != 7) g.lda = 0;
     if (abl != 8) g.ldb = 0;
-    PA_G4A(0);
   }
-  else if (abl == 4) {
-    (void)hipFuncSetAttribute((const void*)gemm4w_kernel<true, false, 0, 5>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                              5 * 32768);
-    hipLaunchKernelGGL((gemm4w_kernel<true, false, 0, 5>), dim3(g.full_tiles), dim3(256), 5 * 32768, st, g);
-  } else PA_G4A(0);
-#undef PA_G4A
-  return (int)hipGetLastError();
+  constexpr int smem = 128 * kEpiRowStride * 4;
+  const dim3 grid(g.full_tiles), block(256);
+  if (abl == 1) return launch_lds<gemm4w_kernel<true, false, 1>>(grid, block, smem, st, g);
+  if (abl == 2) return launch_lds<gemm4w_kernel<true, false, 2>>(grid, block, smem, st, g);
+  if (abl == 3) return launch_lds<gemm4w_kernel<true, false, 3>>(grid, block, smem, st, g);
+  if (abl == 5) return launch_lds<gemm4w_kernel<true, false, 5>>(grid, block, smem, st, g);
+  if (abl == 4) return launch_lds<gemm4w_kernel<true, false, 0, 5>>(grid, block, 5 * 32768, st, g);
+  return launch_lds<gemm4w_kernel<true, false, 0>>(grid, block, smem, st, g);
 }
 
 // C = epi(alpha * A.B). A: [M][K] (a_kmajor) or [K][M]; B: [N][K] (b_kmajor) or [K][N].
@@ -1951,26 +1878,13 @@ PA_EXPORT int pa_gemm_bf16(const void* a, const void* b, void* c, const void* bi
   // partials to c + s * M * ldc (no bias / activation / accumulate); the caller reduces the slabs.
   if (splits < 1) splits = 1;
   if (K % splits != 0) return 1;
-  const int64_t Kc = K / splits;
-  if (Kc % kBK != 0 || N % 8 != 0 || lda % 8 != 0 || ldb % 8 != 0 || ldc % 4 != 0) return 1;
-  if (!a_kmajor && M % 8 != 0) return 1;
   if (splits > 1 && (flags & (kEpiBias | kEpiGelu | kEpiAux | kEpiAccum))) return 1;
   if (splits > 1 && !(flags & kEpiOutF32)) return 1;
+  GemmArgs g;
+  if (!gemm_args(g, a, b, c, bias, aux, M, N, K / splits, lda, ldb, ldc, a_kmajor, flags, alpha)) return 1;
   if (M <= 0 || N <= 0 || K <= 0) return 0;
-  GemmArgs g{};
-  g.a = (const uint16_t*)a; g.b = (const uint16_t*)b; g.c = c;
-  g.bias = (const uint16_t*)bias; g.aux = (uint16_t*)aux;
-  g.lda = lda; g.ldb = ldb; g.ldc = ldc;
-  g.M = (int)M; g.N = (int)N; g.K = (int)Kc;
-  g.flags = flags; g.alpha = alpha;
   g.c_split = M * ldc;
-  // bn: 160 = three-stage 256x160 kernel; 256 / 128 = two-stage kernel with 256x256 / 256x128 tiles;
-  // 1 = 4-phase ping-pong 256x256 kernel
-  if (bn == 160) return dispatch_layout<160>(g, a_kmajor, b_kmajor, splits, st);
-  if (bn == 128) return dispatch_layout<128>(g, a_kmajor, b_kmajor, splits, st);
-  if (bn == 1) return dispatch_layout<0>(g, a_kmajor, b_kmajor, splits, st);
-  if (bn == 4) return dispatch_layout<4>(g, a_kmajor, b_kmajor, splits, st);
-  return dispatch_layout<256>(g, a_kmajor, b_kmajor, splits, st);
+  return launch_bn(g, bn, a_kmajor, b_kmajor, splits, st);
 }
 
 // Implicit-GEMM NDHWC 3-D convolution forward: out[N*Do*Ho*Wo, Cout] = im2col3d(x) . W^T (+ bias), x [N, D, H, W, C]
@@ -1979,16 +1893,10 @@ PA_EXPORT int pa_gemm_bf16(const void* a, const void* b, void* c, const void* bi
 PA_EXPORT int pa_conv3d_ndhwc_fwd(const void* x, const void* w, const void* bias, void* out, const void* zero, int N,
                                   int D, int H, int W, int C, int Cout, int KD, int KH, int KW, int stride, int pad_d,
                                   int pad_h, int pad_w, int dil, int Do, int Ho, int Wo, hipStream_t st) {
-  if (C % kBK != 0 || Cout % 8 != 0 || N <= 0) return 1;
-  GemmArgs g{};
-  g.a = (const uint16_t*)x; g.b = (const uint16_t*)w; g.c = out; g.bias = (const uint16_t*)bias;
-  g.M = N * Do * Ho * Wo; g.N = Cout; g.K = KD * KH * KW * C;
-  g.lda = C; g.ldb = (int64_t)KD * KH * KW * C; g.ldc = Cout;
-  g.flags = bias ? kEpiBias : 0; g.alpha = 1.f;
-  g.zero = (const uint16_t*)zero;
-  g.cD = D; g.cDo = Do; g.cKHW = KH * KW; g.cPadD = pad_d;
-  g.cH = H; g.cW = W; g.cC = C; g.cHo = Ho; g.cWo = Wo; g.cKW = KW; g.cStride = stride; g.cPadH = pad_h;
-  g.cPadW = pad_w; g.cDil = dil;
+  GemmArgs g;
+  if (!conv_fwd_args(g, x, w, bias, out, zero, N, D, H, W, C, Cout, KD, KH, KW, stride, pad_d, pad_h, pad_w, dil, Do,
+                     Ho, Wo, 0))
+    return 1;
   return launch3s<true, true, true>(g, 1, st);
 }
 
@@ -2001,23 +1909,14 @@ PA_EXPORT int pa_gemm_stats_chunks(int64_t M, int bn) { return (int)((M + kBM - 
 PA_EXPORT int pa_gemm_bf16_stats(const void* a, const void* b, void* c, const void* bias, int64_t M, int64_t N,
                                  int64_t K, int64_t lda, int64_t ldb, int64_t ldc, int a_kmajor, int b_kmajor,
                                  int flags, int bn, float* stats, hipStream_t st) {
-  if (K % kBK != 0 || N % 8 != 0 || lda % 8 != 0 || ldb % 8 != 0 || ldc % 4 != 0 || !stats) return 1;
-  if (!a_kmajor && M % 8 != 0) return 1;
-  if (flags & (kEpiOutF32 | kEpiGelu | kEpiAux)) return 1;
+  if (!stats || (flags & (kEpiOutF32 | kEpiGelu | kEpiAux))) return 1;
   if (bn != 160 && bn != 256 && bn != 128 && bn != 4) return 1;
+  GemmArgs g;
+  if (!gemm_args(g, a, b, c, bias, nullptr, M, N, K, lda, ldb, ldc, a_kmajor, flags | kEpiStats, 1.f)) return 1;
   if (M <= 0 || N <= 0 || K <= 0) return 0;
-  GemmArgs g{};
-  g.a = (const uint16_t*)a; g.b = (const uint16_t*)b; g.c = c;
-  g.bias = (const uint16_t*)bias;
-  g.lda = lda; g.ldb = ldb; g.ldc = ldc;
-  g.M = (int)M; g.N = (int)N; g.K = (int)K;
-  g.flags = flags | kEpiStats; g.alpha = 1.f;
   g.c_split = M * ldc;
   g.stats = stats;
-  if (bn == 160) return dispatch_layout<160>(g, a_kmajor, b_kmajor, 1, st);
-  if (bn == 128) return dispatch_layout<128>(g, a_kmajor, b_kmajor, 1, st);
-  if (bn == 4) return dispatch_layout<4>(g, a_kmajor, b_kmajor, 1, st);
-  return dispatch_layout<256>(g, a_kmajor, b_kmajor, 1, st);
+  return launch_bn(g, bn, a_kmajor, b_kmajor, 1, st);
 }
 
 // pa_gemm_bf16_stats in BN-backward form: C is the gradient of a relu'd BN's output (a 1x1 convolution's data
@@ -2026,23 +1925,16 @@ PA_EXPORT int pa_gemm_bf16_stats(const void* a, const void* b, void* c, const vo
 PA_EXPORT int pa_gemm_bf16_bnbwd(const void* a, const void* b, void* c, int64_t M, int64_t N, int64_t K, int64_t lda,
                                  int64_t ldb, int64_t ldc, int a_kmajor, int b_kmajor, int bn, const void* bn_x,
                                  const float* bn_ss, const float* bn_mean, float* stats, hipStream_t st) {
-  if (K % kBK != 0 || N % 8 != 0 || lda % 8 != 0 || ldb % 8 != 0 || ldc % 4 != 0 || !stats) return 1;
-  if (!bn_x || !bn_ss || !bn_mean) return 1;
-  if (!a_kmajor && M % 8 != 0) return 1;
+  if (!stats || !bn_x || !bn_ss || !bn_mean) return 1;
   if (bn != 160 && bn != 256 && bn != 128 && bn != 4) return 1;
+  GemmArgs g;
+  if (!gemm_args(g, a, b, c, nullptr, nullptr, M, N, K, lda, ldb, ldc, a_kmajor, kEpiStats | kEpiStatsBwd, 1.f))
+    return 1;
   if (M <= 0 || N <= 0 || K <= 0) return 0;
-  GemmArgs g{};
-  g.a = (const uint16_t*)a; g.b = (const uint16_t*)b; g.c = c;
-  g.lda = lda; g.ldb = ldb; g.ldc = ldc;
-  g.M = (int)M; g.N = (int)N; g.K = (int)K;
-  g.flags = kEpiStats | kEpiStatsBwd; g.alpha = 1.f;
   g.c_split = M * ldc;
   g.stats = stats;
   g.bn_x = (const uint16_t*)bn_x; g.bn_ss = bn_ss; g.bn_mean = bn_mean;
-  if (bn == 160) return dispatch_layout<160>(g, a_kmajor, b_kmajor, 1, st);
-  if (bn == 128) return dispatch_layout<128>(g, a_kmajor, b_kmajor, 1, st);
-  if (bn == 4) return dispatch_layout<4>(g, a_kmajor, b_kmajor, 1, st);
-  return dispatch_layout<256>(g, a_kmajor, b_kmajor, 1, st);
+  return launch_bn(g, bn, a_kmajor, b_kmajor, 1, st);
 }
 
 // Implicit-GEMM NHWC convolution forward: out[N*Ho*Wo, Cout] = im2col(x) . W^T (+ bias), with
@@ -2051,16 +1943,10 @@ PA_EXPORT int pa_gemm_bf16_bnbwd(const void* a, const void* b, void* c, int64_t 
 PA_EXPORT int pa_conv2d_nhwc_fwd(const void* x, const void* w, const void* bias, void* out, const void* zero, int N,
                                  int H, int W, int C, int Cout, int KH, int KW, int stride, int pad_h, int pad_w,
                                  int dil, int Ho, int Wo, hipStream_t st) {
-  if (C % kBK != 0 || Cout % 8 != 0 || N <= 0) return 1;
-  GemmArgs g{};
-  g.a = (const uint16_t*)x; g.b = (const uint16_t*)w; g.c = out; g.bias = (const uint16_t*)bias;
-  g.M = N * Ho * Wo; g.N = Cout; g.K = KH * KW * C;
-  g.lda = C; g.ldb = (int64_t)KH * KW * C; g.ldc = Cout;
-  g.flags = bias ? kEpiBias : 0; g.alpha = 1.f;
-  g.zero = (const uint16_t*)zero;
-  g.cD = 1; g.cDo = 1; g.cKHW = KH * KW; g.cPadD = 0;
-  g.cH = H; g.cW = W; g.cC = C; g.cHo = Ho; g.cWo = Wo; g.cKW = KW; g.cStride = stride; g.cPadH = pad_h;
-  g.cPadW = pad_w; g.cDil = dil;
+  GemmArgs g;
+  if (!conv_fwd_args(g, x, w, bias, out, zero, N, 1, H, W, C, Cout, 1, KH, KW, stride, 0, pad_h, pad_w, dil, 1, Ho,
+                     Wo, 0))
+    return 1;
   return launch3s<true, true, true>(g, 1, st);
 }
 
@@ -2069,17 +1955,11 @@ PA_EXPORT int pa_conv2d_nhwc_fwd(const void* x, const void* w, const void* bias,
 PA_EXPORT int pa_conv2d_nhwc_fwd_stats(const void* x, const void* w, const void* bias, void* out, const void* zero,
                                        int N, int H, int W, int C, int Cout, int KH, int KW, int stride, int pad_h,
                                        int pad_w, int dil, int Ho, int Wo, float* stats, hipStream_t st) {
-  if (C % kBK != 0 || Cout % 8 != 0 || N <= 0 || !stats) return 1;
-  GemmArgs g{};
-  g.a = (const uint16_t*)x; g.b = (const uint16_t*)w; g.c = out; g.bias = (const uint16_t*)bias;
-  g.M = N * Ho * Wo; g.N = Cout; g.K = KH * KW * C;
-  g.lda = C; g.ldb = (int64_t)KH * KW * C; g.ldc = Cout;
-  g.flags = (bias ? kEpiBias : 0) | kEpiStats; g.alpha = 1.f;
+  GemmArgs g;
+  if (!stats || !conv_fwd_args(g, x, w, bias, out, zero, N, 1, H, W, C, Cout, 1, KH, KW, stride, 0, pad_h, pad_w, dil,
+                               1, Ho, Wo, kEpiStats))
+    return 1;
   g.stats = stats;
-  g.zero = (const uint16_t*)zero;
-  g.cD = 1; g.cDo = 1; g.cKHW = KH * KW; g.cPadD = 0;
-  g.cH = H; g.cW = W; g.cC = C; g.cHo = Ho; g.cWo = Wo; g.cKW = KW; g.cStride = stride; g.cPadH = pad_h;
-  g.cPadW = pad_w; g.cDil = dil;
   return launch3s<true, true, true>(g, 1, st);
 }
 
@@ -2089,18 +1969,13 @@ PA_EXPORT int pa_conv2d_nhwc_fwd_bnbwd(const void* x, const void* w, void* out, 
                                        int C, int Cout, int KH, int KW, int stride, int pad_h, int pad_w, int dil,
                                        int Ho, int Wo, const void* bn_x, const float* bn_ss, const float* bn_mean,
                                        float* stats, hipStream_t st) {
-  if (C % kBK != 0 || Cout % 8 != 0 || N <= 0 || !stats || !bn_x || !bn_ss || !bn_mean) return 1;
-  GemmArgs g{};
-  g.a = (const uint16_t*)x; g.b = (const uint16_t*)w; g.c = out;
-  g.M = N * Ho * Wo; g.N = Cout; g.K = KH * KW * C;
-  g.lda = C; g.ldb = (int64_t)KH * KW * C; g.ldc = Cout;
-  g.flags = kEpiStats | kEpiStatsBwd; g.alpha = 1.f;
+  GemmArgs g;
+  if (!stats || !bn_x || !bn_ss || !bn_mean) return 1;
+  if (!conv_fwd_args(g, x, w, nullptr, out, zero, N, 1, H, W, C, Cout, 1, KH, KW, stride, 0, pad_h, pad_w, dil, 1, Ho,
+                     Wo, kEpiStats | kEpiStatsBwd))
+    return 1;
   g.stats = stats;
   g.bn_x = (const uint16_t*)bn_x; g.bn_ss = bn_ss; g.bn_mean = bn_mean;
-  g.zero = (const uint16_t*)zero;
-  g.cD = 1; g.cDo = 1; g.cKHW = KH * KW; g.cPadD = 0;
-  g.cH = H; g.cW = W; g.cC = C; g.cHo = Ho; g.cWo = Wo; g.cKW = KW; g.cStride = stride; g.cPadH = pad_h;
-  g.cPadW = pad_w; g.cDil = dil;
   return launch3s<true, true, true>(g, 1, st);
 }
 
@@ -2113,35 +1988,19 @@ PA_EXPORT int pa_conv2d_nhwc_wgrad(const void* x, const void* dy, float* ws, con
   const int64_t P = (int64_t)N * Ho * Wo;
   if (C % 8 || Cout % 8 || splits < 1 || P % (64 * splits) || P / splits > 0x7fffffff) return 1;
   if (bn != 64 && bn != 128 && bn != 256) return 2;
-  GemmArgs g{};
-  g.a = (const uint16_t*)x; g.b = (const uint16_t*)dy; g.c = ws;
-  g.lda = 0; g.ldb = Cout; g.ldc = Cout;
-  g.M = KH * KW * C; g.N = Cout; g.K = (int)(P / splits);
-  g.flags = kEpiOutF32; g.alpha = 1.f;
+  GemmArgs g;
+  if (!gemm_args(g, x, dy, ws, nullptr, nullptr, (int64_t)KH * KW * C, Cout, P / splits, 0, Cout, Cout, 0, kEpiOutF32,
+                 1.f))
+    return 1;
   g.c_split = (int64_t)g.M * Cout;
-  g.zero = (const uint16_t*)zero;
-  g.cD = 1; g.cDo = 1; g.cKHW = KH * KW; g.cPadD = 0;
-  g.cH = H; g.cW = W; g.cC = C; g.cHo = Ho; g.cWo = Wo; g.cKW = KW; g.cStride = stride; g.cPadH = pad_h;
-  g.cPadW = pad_w; g.cDil = dil;
+  set_conv_geometry(g, zero, 1, H, W, C, 1, Ho, Wo, KH, KW, stride, 0, pad_h, pad_w, dil);
   g.tiles_m = (g.M + kBM - 1) / kBM;
   g.tiles_n = (g.N + bn - 1) / bn;
+  const dim3 grid(g.tiles_m * g.tiles_n, splits), block(512);
   const int smem = 2 * (kBM + bn) * kBK * 2;
-  static bool attr_set[3] = {false, false, false};
-#define PA_WG(BNV, I)                                                                                           \
-  do {                                                                                                          \
-    if (!attr_set[I]) {                                                                                         \
-      (void)hipFuncSetAttribute((const void*)gemm_bf16_kernel<BNV, false, false, 8, true>,                      \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, smem);                              \
-      attr_set[I] = true;                                                                                       \
-    }                                                                                                           \
-    hipLaunchKernelGGL((gemm_bf16_kernel<BNV, false, false, 8, true>), dim3(g.tiles_m * g.tiles_n, splits),     \
-                       dim3(512), smem, st, g);                                                                 \
-  } while (0)
-  if (bn == 256) PA_WG(256, 1);
-  else if (bn == 64) PA_WG(64, 2);
-  else PA_WG(128, 0);
-#undef PA_WG
-  return (int)hipGetLastError();
+  if (bn == 256) return launch_lds<gemm_bf16_kernel<256, false, false, 8, true>>(grid, block, smem, st, g);
+  if (bn == 64) return launch_lds<gemm_bf16_kernel<64, false, false, 8, true>>(grid, block, smem, st, g);
+  return launch_lds<gemm_bf16_kernel<128, false, false, 8, true>>(grid, block, smem, st, g);
 }
 
 // Decode-shape GEMM: c[M, N] (bf16, row stride ldc) = a[M, K] (K-major) . b[K, N] (N-major) (+ bias),
@@ -2152,22 +2011,14 @@ PA_EXPORT int pa_gemm_small_m(const void* a, int64_t lda, const void* b, int64_t
   if (stages != 3 && stages != 4) return 2;
   // 4 stages: 96 KiB LDS, one workgroup per CU; 3 stages: 72 KiB, two per CU
   const int smem = stages * (kSmBM + kSmBN) * kBK * 2;
-  static bool attr_set[2] = {false, false};
   const dim3 grid((N + kSmBN - 1) / kSmBN, splits), block(kSmNW * 64);
-#define PA_SMM(S)                                                                                                \
-  do {                                                                                                          \
-    if (!attr_set[S - 3]) {                                                                                     \
-      (void)hipFuncSetAttribute((const void*)gemm_small_m_kernel<S>, hipFuncAttributeMaxDynamicSharedMemorySize, \
-                                smem);                                                                          \
-      attr_set[S - 3] = true;                                                                                   \
-    }                                                                                                           \
-    hipLaunchKernelGGL(gemm_small_m_kernel<S>, grid, block, smem, st, (const uint16_t*)a, lda, (const uint16_t*)b, \
-                       ldb, ws, M, N, K / splits, (const uint16_t*)bias, (uint16_t*)c, ldc);                    \
-  } while (0)
-  if (stages == 3) PA_SMM(3);
-  else PA_SMM(4);
-#undef PA_SMM
-  if (splits == 1) return (int)hipGetLastError();
+  const auto run = [&](auto stg) {
+    return launch_lds<gemm_small_m_kernel<decltype(stg)::value>>(grid, block, smem, st, (const uint16_t*)a, lda,
+                                                                 (const uint16_t*)b, ldb, ws, M, N, K / splits,
+                                                                 (const uint16_t*)bias, (uint16_t*)c, ldc);
+  };
+  const int rc = stages == 3 ? run(IntC<3>{}) : run(IntC<4>{});
+  if (rc || splits == 1) return rc;
   const int64_t n4 = (int64_t)M * N / 4;
   hipLaunchKernelGGL(gemm_small_m_reduce_k, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, st, ws,
                      (const uint16_t*)bias, (uint16_t*)c, ldc, M, N, splits);

@@ -17,6 +17,8 @@
 // no scale placement matters). Operands are swapped (D = B-frag x A-frag) so a lane ends with 4
 // consecutive columns of one output row.
 #include "common.h"
+#include "gemm_plan.h"
+#include "launch.h"
 
 using namespace pa;
 
@@ -284,33 +286,6 @@ __global__ __launch_bounds__(256) void gemm_fp8_tail_reduce_k(Fp8Args p) {
               : make_uint2(pack_bf16(v[0], v[1]), pack_bf16(v[2], v[3]));
 }
 
-int device_cus8() {
-  static int cus = 0;
-  if (!cus) {
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
-  }
-  return cus;
-}
-
-// tail plan: the remainder of the last whole wave of tiles is cut along K so the last wave fills the chip (only
-// when it covers at most half of it and every slice keeps at least 4 K-tiles of 128)
-void pp_plan8(int64_t M, int64_t N, int64_t K, int cus, int* full, int* split) {
-  const int64_t T = ((M + 255) / 256) * ((N + 255) / 256);
-  const int64_t nk = K / kKB;
-  *full = (int)T;
-  *split = 0;
-  if (T <= cus) return;
-  const int64_t r = T % cus;
-  if (r == 0 || 2 * r > cus) return;
-  int sp = 1;
-  while (r * sp * 2 <= cus && nk % (sp * 2) == 0 && nk / (sp * 2) >= 4) sp *= 2;
-  if (sp == 1) return;
-  *full = (int)(T - r);
-  *split = sp;
-}
-
 constexpr int kPPThreads = 512;
 constexpr int kEpiRS = 264;  // 16-bit values per row of the epilogue image (528-byte rows)
 
@@ -536,41 +511,25 @@ __global__ __launch_bounds__(kPPThreads, 1) void gemm_fp8_pp_kernel(Fp8Args p) {
   }
 }
 
+// ping-pong kernel with the balanced tail pl (the plan g.full_tiles / g.tail_split were filled from)
 template <int FA, int FB, bool F16>
-int launch_pp(const Fp8Args& g, hipStream_t st) {
-  static bool attr = false;
+int launch_pp(const Fp8Args& g, const TailPlan& pl, hipStream_t st) {
   // two 64-KiB stages; the epilogue image [256][264] x 2 B (132 KiB) reuses them and is the larger
   constexpr int smem = (2 * 4 * 128 * kKB) > (kTile * kEpiRS * 2) ? (2 * 4 * 128 * kKB) : (kTile * kEpiRS * 2);
-  if (!attr) {
-    (void)hipFuncSetAttribute((const void*)gemm_fp8_pp_kernel<FA, FB, F16>,
-                              hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-    attr = true;
-  }
-  const int T = g.tiles_m * g.tiles_n;
-  const int grid = g.tail_split ? g.full_tiles + (T - g.full_tiles) * g.tail_split : T;
-  hipLaunchKernelGGL((gemm_fp8_pp_kernel<FA, FB, F16>), dim3(grid), dim3(kPPThreads), smem, st, g);
-  int rc = (int)hipGetLastError();
-  if (rc || !g.tail_split) return rc;
-  hipLaunchKernelGGL((gemm_fp8_tail_reduce_k<F16>), dim3(T - g.full_tiles, 64), dim3(256), 0, st, g);
+  const int rc = launch_lds<gemm_fp8_pp_kernel<FA, FB, F16>>(dim3(pl.grid), dim3(kPPThreads), smem, st, g);
+  if (rc || !pl.split) return rc;
+  hipLaunchKernelGGL((gemm_fp8_tail_reduce_k<F16>), dim3(pl.tiles - pl.full_tiles, 64), dim3(256), 0, st, g);
   return (int)hipGetLastError();
 }
 
 template <int FA, int FB, bool F16>
 int launch(const Fp8Args& g, hipStream_t st) {
-  static bool attr = false;
-  constexpr int smem = 2 * kStage;
-  if (!attr) {
-    (void)hipFuncSetAttribute((const void*)gemm_fp8_kernel<FA, FB, F16>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                              smem);
-    attr = true;
-  }
-  hipLaunchKernelGGL((gemm_fp8_kernel<FA, FB, F16>), dim3(g.tiles_m * g.tiles_n), dim3(512), smem, st, g);
-  return (int)hipGetLastError();
+  return launch_lds<gemm_fp8_kernel<FA, FB, F16>>(dim3(g.tiles_m * g.tiles_n), dim3(512), 2 * kStage, st, g);
 }
 
 template <int FA, int FB>
-int launch_out(const Fp8Args& g, int out_f16, bool pp, hipStream_t st) {
-  if (pp) return out_f16 ? launch_pp<FA, FB, true>(g, st) : launch_pp<FA, FB, false>(g, st);
+int launch_out(const Fp8Args& g, int out_f16, bool pp, const TailPlan& pl, hipStream_t st) {
+  if (pp) return out_f16 ? launch_pp<FA, FB, true>(g, pl, st) : launch_pp<FA, FB, false>(g, pl, st);
   return out_f16 ? launch<FA, FB, true>(g, st) : launch<FA, FB, false>(g, st);
 }
 
@@ -583,11 +542,7 @@ int g_fp8_kernel = 0;
 // Returns 1 for an unsupported shape / stride (K % 128, N % 4, leading dims % 16 bytes).
 // Workspace (bytes) the ping-pong fp8 GEMM's balanced tail needs (0: none).
 PA_EXPORT int64_t pa_gemm_fp8_ws_bytes(int64_t M, int64_t N, int64_t K) {
-  int full, split;
-  pp_plan8(M, N, K, device_cus8(), &full, &split);
-  if (!split) return 0;
-  const int64_t T = ((M + 255) / 256) * ((N + 255) / 256);
-  return (T - full) * split * 65536 * 4;
+  return tail_plan(M, N, K, kKB, device_cus()).ws_bytes;
 }
 
 static int fp8_impl(const void* a, const void* b, void* c, const void* bias, int64_t M, int64_t N, int64_t K,
@@ -621,21 +576,15 @@ static int fp8_impl(const void* a, const void* b, void* c, const void* bias, int
   g.tiles_n = (int)((N + kTile - 1) / kTile);
   g.alpha = alpha; g.act = act;
   const bool pp = g_fp8_kernel != 1 && N % 8 == 0 && ldc % 8 == 0;
-  g.full_tiles = g.tiles_m * g.tiles_n;
-  g.tail_split = 0;
-  if (pp && ws) {
-    int full, split;
-    pp_plan8(M, N, K, device_cus8(), &full, &split);
-    if (split) {
-      g.full_tiles = full;
-      g.tail_split = split;
-      g.tail_ws = (float*)ws;
-    }
-  }
-  if (fmt_a == 0 && fmt_b == 0) return launch_out<0, 0>(g, out_f16, pp, st);
-  if (fmt_a == 0 && fmt_b == 1) return launch_out<0, 1>(g, out_f16, pp, st);
-  if (fmt_a == 1 && fmt_b == 0) return launch_out<1, 0>(g, out_f16, pp, st);
-  return launch_out<1, 1>(g, out_f16, pp, st);
+  TailPlan pl = tail_plan(M, N, K, kKB, device_cus());
+  if (!pp || !ws) pl = without_tail(pl);
+  g.full_tiles = pl.full_tiles;
+  g.tail_split = pl.split;
+  g.tail_ws = pl.split ? (float*)ws : nullptr;
+  if (fmt_a == 0 && fmt_b == 0) return launch_out<0, 0>(g, out_f16, pp, pl, st);
+  if (fmt_a == 0 && fmt_b == 1) return launch_out<0, 1>(g, out_f16, pp, pl, st);
+  if (fmt_a == 1 && fmt_b == 0) return launch_out<1, 0>(g, out_f16, pp, pl, st);
+  return launch_out<1, 1>(g, out_f16, pp, pl, st);
 }
 
 // 0 auto, 1 generic kernel only (A/B and tests)

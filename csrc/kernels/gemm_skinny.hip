@@ -219,14 +219,15 @@ __global__ __launch_bounds__(256) void skinny_gemm_k(SkArgs p) {
 }
 
 // Opt a kernel into 160 KB of dynamic LDS once per device (the attribute is per device; one process may drive
-// several GPUs). Bit d of `done` marks device d.
-__host__ inline void sk_lds_attr(const void* fn, unsigned long long& done) {
+// several GPUs, which launch_lds of launch.h does not cover). Bit d of `done` marks device d. false: the call failed.
+__host__ inline bool sk_lds_attr(const void* fn, unsigned long long& done) {
   int dev = 0;
   (void)hipGetDevice(&dev);
   const unsigned long long bit = 1ull << (dev & 63);
-  if (done & bit) return;
-  (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+  if (done & bit) return true;
+  if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) return false;
   done |= bit;
+  return true;
 }
 
 // workgroups of a skinny_gemm_k launch (the statistics variant writes 4 chunks per workgroup)
@@ -247,7 +248,7 @@ int launch_sk(const SkArgs& a, hipStream_t st) {
   if (lds > 160 * 1024) return 2;
   const int64_t grid = sk_grid(a.M, N, K);
   static unsigned long long attr_done = 0;  // devices whose LDS limit this instantiation raised
-  sk_lds_attr(reinterpret_cast<const void*>(&skinny_gemm_k<NT, KS, R, STATS>), attr_done);
+  if (!sk_lds_attr(reinterpret_cast<const void*>(&skinny_gemm_k<NT, KS, R, STATS>), attr_done)) return 1;
   hipLaunchKernelGGL((skinny_gemm_k<NT, KS, R, STATS>), dim3((unsigned)grid), dim3(256), lds, st, a);
   PA_CHECK_LAUNCH();
   return 0;
@@ -414,7 +415,7 @@ int launch_skconv(const SkConvArgs& a, hipStream_t st) {
   const int64_t nb = (a.M + 16 * R - 1) / (16 * R);
   const int64_t grid = std::min<int64_t>((nb + NW - 1) / NW, (int64_t)256 * per_cu);
   static unsigned long long attr_done = 0;  // devices whose LDS limit this instantiation raised
-  sk_lds_attr(reinterpret_cast<const void*>(&skinny_conv_k<NT, C, KH, KW, R, NW>), attr_done);
+  if (!sk_lds_attr(reinterpret_cast<const void*>(&skinny_conv_k<NT, C, KH, KW, R, NW>), attr_done)) return 1;
   hipLaunchKernelGGL((skinny_conv_k<NT, C, KH, KW, R, NW>), dim3((unsigned)grid), dim3(NW * 64), lds, st, a);
   PA_CHECK_LAUNCH();
   return 0;
@@ -585,7 +586,7 @@ int launch_halo(const SkHaloArgs& a, hipStream_t st) {
   if (lds > 160 * 1024) return 2;
   const int64_t grid = halo_grid<NW, R>(a.N, a.H, a.W);
   static unsigned long long attr_done = 0;
-  sk_lds_attr(reinterpret_cast<const void*>(&skinny_conv_halo_k<NW, R, STATS>), attr_done);
+  if (!sk_lds_attr(reinterpret_cast<const void*>(&skinny_conv_halo_k<NW, R, STATS>), attr_done)) return 1;
   hipLaunchKernelGGL((skinny_conv_halo_k<NW, R, STATS>), dim3((unsigned)grid), dim3(NW * 64), lds, st, a);
   PA_CHECK_LAUNCH();
   return 0;

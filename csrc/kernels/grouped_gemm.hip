@@ -20,6 +20,7 @@
 // global -> LDS with global_load_lds_dwordx4 into two stages, K-major images XOR-swizzled per 16-B chunk,
 // MN-major images read with ds_read_b64_tr_b16.
 #include "common.h"
+#include "launch.h"
 
 using namespace pa;
 
@@ -247,15 +248,8 @@ __global__ __launch_bounds__(NW * 64, (BM * BN > 128 * 128 ? 1 : 2)) void groupe
 template <int MODE, int BM, int BN, int NW>
 int launch_gg(const GGArgs& a, int grid, hipStream_t st) {
   constexpr int smem = 2 * (BM + BN) * kK * 2;
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute((const void*)grouped_gemm_kernel<MODE, BM, BN, NW>,
-                              hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-    attr_set = true;
-  }
   if (grid <= 0) return 0;
-  hipLaunchKernelGGL((grouped_gemm_kernel<MODE, BM, BN, NW>), dim3((unsigned)grid), dim3(NW * 64), smem, st, a);
-  return (int)hipGetLastError();
+  return launch_lds<grouped_gemm_kernel<MODE, BM, BN, NW>>(dim3((unsigned)grid), dim3(NW * 64), smem, st, a);
 }
 
 // ---- routing: expert id per (token, slot) entry -> counts, offsets, stable permutation.

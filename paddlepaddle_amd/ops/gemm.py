@@ -32,6 +32,20 @@ def _layout(t, outer_dim):
     return None
 
 
+def _operands(a, b):
+    """(M, N, K, lda, a_kmajor, ldb, b_kmajor) of the product a @ b as the launchers take it."""
+    M, K = a.shape
+    lda, ak = _layout(a, 0)
+    ldb, bk = _layout(b, 1)
+    return M, b.shape[1], K, lda, ak, ldb, bk
+
+
+def _pp_workspace(M, N, K, device):
+    """The balanced-tail workspace of the 256x256 kernels (pa_gemm_pp_ws_bytes); None when the plan has no tail."""
+    nb = int(L.lib().pa_gemm_pp_ws_bytes(M, N, K))
+    return torch.empty(nb // 4, dtype=torch.float32, device=device) if nb else None
+
+
 def supported(a, b, out_dtype=None):
     """Shape/layout/dtype conditions of the HIP kernel for C = a @ b."""
     if a.dim() != 2 or b.dim() != 2 or a.dtype != torch.bfloat16 or b.dtype != torch.bfloat16:
@@ -55,10 +69,7 @@ def supported(a, b, out_dtype=None):
 def gemm(a, b, bias=None, gelu=False, aux=None, out=None, accumulate=False, alpha=1.0, out_dtype=None, bn=None):
     """C = epi(alpha * a @ b). ``aux`` (bf16 [M, N]) receives the pre-activation when ``gelu``;
     ``accumulate`` adds into ``out`` (bf16 or fp32, [M, N] contiguous rows)."""
-    M, K = a.shape
-    N = b.shape[1]
-    lda, ak = _layout(a, 0)
-    ldb, bk = _layout(b, 1)
+    M, N, K, lda, ak, ldb, bk = _operands(a, b)
     if out is None:
         out = torch.empty(M, N, dtype=out_dtype or torch.bfloat16, device=a.device)
     assert out.stride(1) == 1 and out.stride(0) % 4 == 0
@@ -78,8 +89,7 @@ def gemm(a, b, bias=None, gelu=False, aux=None, out=None, accumulate=False, alph
         bn = _pick_bn(M, N, bk)
     if bn in (1, 2) and L.has("pa_gemm_bf16_pp"):
         # 256x256 + balanced tail: 1 8-wave ping-pong, 2 4-wave K32 ring
-        nb = int(L.lib().pa_gemm_pp_ws_bytes(M, N, K))
-        ws = torch.empty(nb // 4, dtype=torch.float32, device=a.device) if nb else None
+        ws = _pp_workspace(M, N, K, a.device)
         fn = {1: "pa_gemm_bf16_pp", 2: "pa_gemm_bf16_4w"}[bn]
         L.call(fn, L.ptr(a), L.ptr(b), L.ptr(out), L.ptr(bias),
                L.ptr(aux), M, N, K, lda, ldb, out.stride(0), int(ak), int(bk), flags, float(alpha), L.ptr(ws),
@@ -100,13 +110,9 @@ def res_supported(a, b, res):
 def gemm_res(a, b, res, bias=None):
     """a @ b (+ bias) + res in one launch (csrc/kernels/gemm.hip pa_gemm_bf16_res: the residual is read by the
     epilogue), ping-pong kernel with its balanced tail."""
-    M, K = a.shape
-    N = b.shape[1]
-    lda, ak = _layout(a, 0)
-    ldb, bk = _layout(b, 1)
+    M, N, K, lda, ak, ldb, bk = _operands(a, b)
     out = torch.empty(M, N, dtype=torch.bfloat16, device=a.device)
-    nb = int(L.lib().pa_gemm_pp_ws_bytes(M, N, K))
-    ws = torch.empty(nb // 4, dtype=torch.float32, device=a.device) if nb else None
+    ws = _pp_workspace(M, N, K, a.device)
     L.call("pa_gemm_bf16_res", L.ptr(a), L.ptr(b), L.ptr(out), L.ptr(bias), L.ptr(res), M, N, K, lda, ldb, N,
            int(ak), int(bk), L.ptr(ws), L.stream_ptr())
     return out
@@ -123,10 +129,7 @@ def gemm_dgelu(a, b, pre, kern=1):
     """(dh, parts): dh = (a @ b) * gelu_tanh'(pre) (bf16) and the per-256-row-tile column sums of dh
     (fp32 [ceil(M / 256), N]; fold with pa_fold_partials for the bias gradient). kern: 1 ping-pong, 2 4-wave K32
     (csrc/kernels/gemm.hip pa_gemm_bf16_dgelu)."""
-    M, K = a.shape
-    N = b.shape[1]
-    lda, ak = _layout(a, 0)
-    ldb, bk = _layout(b, 1)
+    M, N, K, lda, ak, ldb, bk = _operands(a, b)
     dh = torch.empty(M, N, dtype=torch.bfloat16, device=a.device)
     parts = torch.empty(-(-M // 256), N, dtype=torch.float32, device=a.device)
     L.call("pa_gemm_bf16_dgelu", L.ptr(a), L.ptr(b), L.ptr(dh), L.ptr(pre), L.ptr(parts), M, N, K, lda, ldb, N,
@@ -161,7 +164,7 @@ def gemm_kseg(As, Bs, out=None, accumulate=False, alpha=1.0):
     operand pair of their segment (csrc/kernels/gemm.hip pa_gemm_bf16_pp_segs, seg_k = 1): the data gradient of
     sibling linears that share an input (dx = sum dy_i W_i^T), the weight gradients of two accumulation micro-batches
     (ops/linear.py pair_weight_grads) — one launch, one output pass, no concatenated copies."""
-    M, N = As[0].shape[0], Bs[0].shape[1]
+    M, N, _, lda, ak, ldb, bk = _operands(As[0], Bs[0])
     K = sum(a.shape[1] for a in As)
     if out is None:
         out = torch.empty(M, N, dtype=torch.bfloat16, device=As[0].device)
@@ -170,16 +173,11 @@ def gemm_kseg(As, Bs, out=None, accumulate=False, alpha=1.0):
     for a, b in zip(As, Bs):
         end += a.shape[1]
         rows.append([a.data_ptr(), b.data_ptr(), _layout(a, 0)[0], _layout(b, 1)[0], end])
-    ak, bk = _layout(As[0], 0)[1], _layout(Bs[0], 1)[1]
     flags = (EPI_ACCUM if accumulate else 0) | (EPI_OUT_F32 if out.dtype == torch.float32 else 0)
-    nb = int(L.lib().pa_gemm_pp_ws_bytes(M, N, K))
-    ws = torch.empty(nb // 4, dtype=torch.float32, device=out.device) if nb else None
+    ws = _pp_workspace(M, N, K, out.device)
     tab = _seg_table(rows)
-    rc = L.call("pa_gemm_bf16_pp_segs", tab.data_ptr(), len(rows), 1, L.ptr(As[0]), L.ptr(Bs[0]), L.ptr(out),
-                L.ptr(None), M, N, K, rows[0][2], rows[0][3], out.stride(0), int(ak), int(bk), flags, float(alpha),
-                L.ptr(ws), L.stream_ptr())
-    if rc:
-        raise RuntimeError(f"pa_gemm_bf16_pp_segs (K) failed ({rc}) for M={M} N={N} K={K}")
+    L.call("pa_gemm_bf16_pp_segs", tab.data_ptr(), len(rows), 1, L.ptr(As[0]), L.ptr(Bs[0]), L.ptr(out), L.ptr(None),
+           M, N, K, lda, ldb, out.stride(0), int(ak), int(bk), flags, float(alpha), L.ptr(ws), L.stream_ptr())
     return out
 
 
@@ -205,7 +203,7 @@ def gemm_nseg(a, Bs, out=None, alpha=1.0):
     """C [M, sum N_i] = alpha * a @ [Bs[0] | Bs[1] | ...] as ONE GEMM whose column tiles read the weight of their
     segment (pa_gemm_bf16_pp_segs, seg_k = 0): the q / k / v or gate / up projections of one input with separate
     weight tensors, no concatenated weight copy; the per-projection outputs are column views of C."""
-    M, K = a.shape
+    M, _, K, lda, ak, ldb, bk = _operands(a, Bs[0])
     N = sum(b.shape[1] for b in Bs)
     if out is None:
         out = torch.empty(M, N, dtype=torch.bfloat16, device=a.device)
@@ -214,17 +212,11 @@ def gemm_nseg(a, Bs, out=None, alpha=1.0):
     for b in Bs:
         end += b.shape[1]
         rows.append([a.data_ptr(), b.data_ptr(), _layout(a, 0)[0], _layout(b, 1)[0], end])
-    lda, ak = _layout(a, 0)
-    bk = _layout(Bs[0], 1)[1]
     flags = EPI_OUT_F32 if out.dtype == torch.float32 else 0
-    nb = int(L.lib().pa_gemm_pp_ws_bytes(M, N, K))
-    ws = torch.empty(nb // 4, dtype=torch.float32, device=a.device) if nb else None
+    ws = _pp_workspace(M, N, K, a.device)
     tab = _seg_table(rows)
-    rc = L.call("pa_gemm_bf16_pp_segs", tab.data_ptr(), len(rows), 0, L.ptr(a), L.ptr(Bs[0]), L.ptr(out),
-                L.ptr(None), M, N, K, lda, rows[0][3], out.stride(0), int(ak), int(bk), flags, float(alpha),
-                L.ptr(ws), L.stream_ptr())
-    if rc:
-        raise RuntimeError(f"pa_gemm_bf16_pp_segs (N) failed ({rc}) for M={M} N={N} K={K}")
+    L.call("pa_gemm_bf16_pp_segs", tab.data_ptr(), len(rows), 0, L.ptr(a), L.ptr(Bs[0]), L.ptr(out), L.ptr(None),
+           M, N, K, lda, ldb, out.stride(0), int(ak), int(bk), flags, float(alpha), L.ptr(ws), L.stream_ptr())
     return out
 
 
@@ -241,10 +233,7 @@ def gemm_bn_stats(a, b, bias=None, bn=None):
     """C = a @ b (+ bias) in bf16 plus the batch-norm partials of C's columns, written by the GEMM epilogue
     (kEpiStats): returns (C, stats [2 * chunks * N] fp32, chunks) for ops/bn.py (conv -> BN fusion).
     bn: tile width (160: three-stage kernel; 128 / 256: two-stage kernel), default by layout."""
-    M, K = a.shape
-    N = b.shape[1]
-    lda, ak = _layout(a, 0)
-    ldb, bk = _layout(b, 1)
+    M, N, K, lda, ak, ldb, bk = _operands(a, b)
     if bn is None:
         bn = 160 if bk else (256 if _pick_bn(M, N, bk) == 256 else 128)
     chunks = int(L.lib().pa_gemm_stats_chunks(M, bn))
@@ -258,10 +247,7 @@ def gemm_bn_stats(a, b, bias=None, bn=None):
 def gemm_splitk(a, b, splits, out_dtype=torch.bfloat16, bn=None):
     """C = a @ b with K split over ``splits`` slices computed by separate workgroups (fp32 slabs, summed
     here): fills the chip when M x N has few tiles but K is long (weight gradients of convolutions)."""
-    M, K = a.shape
-    N = b.shape[1]
-    lda, ak = _layout(a, 0)
-    ldb, bk = _layout(b, 1)
+    M, N, K, lda, ak, ldb, bk = _operands(a, b)
     ws = torch.empty(splits, M, N, dtype=torch.float32, device=a.device)
     if bn is None:
         bn = _pick_bn(M, N, bk)
@@ -296,10 +282,7 @@ def gemm_pp_splitk(a, b, splits, out_dtype=torch.bfloat16, out=None, accumulate=
     """C = a @ b on the ping-pong 256x256 kernel with every tile cut into ``splits`` K slices (fp32 partial tiles
     summed, with the cast, by the tail-reduction kernel): the split-K form for few output tiles and a long K.
     ``out`` + ``accumulate``: C += a @ b in place (the reduction reads C; gradient-accumulation fusion)."""
-    M, K = a.shape
-    N = b.shape[1]
-    lda, ak = _layout(a, 0)
-    ldb, bk = _layout(b, 1)
+    M, N, K, lda, ak, ldb, bk = _operands(a, b)
     if out is None:
         out = torch.empty(M, N, dtype=out_dtype, device=a.device)
     elif out.shape != (M, N) or out.stride(1) != 1 or out.stride(0) % 4 or out.dtype not in (torch.bfloat16,
@@ -345,10 +328,8 @@ def gemm_skinny(a, b, bias=None, out=None, accumulate=False, relu=False):
     bk = b.stride(0) == 1  # b = B^T row-major viewed transposed
     ldb = b.stride(1) if bk else b.stride(0)
     flags = (1 if bias is not None else 0) | (2 if accumulate else 0) | (4 if relu else 0)
-    rc = L.call("pa_gemm_skinny", L.ptr(a), L.ptr(b), L.ptr(out), L.ptr(bias), M, N, K, a.stride(0), ldb,
-                out.stride(0), int(bk), flags, L.stream_ptr())
-    if rc:
-        raise RuntimeError(f"pa_gemm_skinny failed ({rc}) for M={M} N={N} K={K}")
+    L.call("pa_gemm_skinny", L.ptr(a), L.ptr(b), L.ptr(out), L.ptr(bias), M, N, K, a.stride(0), ldb, out.stride(0),
+           int(bk), flags, L.stream_ptr())
     return out
 
 
