@@ -3,9 +3,11 @@
 Reference: paddle/phi/kernels/gpu/fused_adam_kernel.cu (multi-tensor Adam/AdamW with master
 weights), adamw_kernel.cu.
 Kernel: csrc/kernels/adamw.hip — one launch updates every tensor of a parameter group:
-a device-side table of {param_fp32, grad, m, v, param_lowp, numel} entries, workgroups walk
-fixed 64 KiB chunks (persistent-style work list computed on the host once and cached), fp32
-math, optional bf16/fp16 shadow copy written in the same pass, grads unscaled by 1/loss_scale.
+a device-side table of {param_fp32, grad, m, v, param_lowp, numel, dtypes, wd, lr_mult} rows,
+workgroups walk fixed 16384-element chunks (persistent-style work list computed on the host once
+and cached), fp32 math, optional bf16/fp16 shadow copy written in the same pass, grads unscaled
+by 1/loss_scale. The optimizers (optimizer/adam.py, optimizer/others.py) build their own row
+tables; this module holds the table upload and the multi-tensor sum of squares.
 """
 from __future__ import annotations
 
@@ -32,49 +34,6 @@ def device_table(rows, dev):
     return host.to(dev, non_blocking=True), host
 
 
-class AdamWTable:
-    """Device-resident pointer table for one parameter group (rebuilt when buffers change)."""
-
-    def __init__(self, params, grads, ms, vs, lowps):
-        self.key = tuple(t.data_ptr() for t in params) + tuple(g.data_ptr() for g in grads)
-        rows = []
-        items = []
-        for i, (p, g, m, v, lp) in enumerate(zip(params, grads, ms, vs, lowps)):
-            n = p.numel()
-            gdt = {torch.float32: 0, torch.float16: 1, torch.bfloat16: 2}[g.dtype]
-            ldt = 3 if lp is None else {torch.float32: 0, torch.float16: 1, torch.bfloat16: 2}[lp.dtype]
-            rows.append([p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(),
-                         0 if lp is None else lp.data_ptr(), n, gdt | (ldt << 8)])
-            for s in range(0, n, _CHUNK):
-                items.append([i, s])
-        dev = params[0].device
-        self.table = torch.tensor(rows, dtype=torch.int64).to(dev)
-        self.items = torch.tensor(items, dtype=torch.int64).to(dev)
-        self.n_items = len(items)
-
-
-def adamw_step_hip(table, lr, beta1, beta2, eps, weight_decay, bc1, bc2, grad_scale_inv_ptr=None):
-    L.call("pa_adamw_multi", L.ptr(table.table), L.ptr(table.items), table.n_items,
-           ctypes.c_void_p(0) if grad_scale_inv_ptr is None else L.ptr(grad_scale_inv_ptr),
-           float(lr), float(beta1), float(beta2), float(eps), float(weight_decay), float(bc1), float(bc2),
-           ctypes.c_void_p(0), L.stream_ptr())
-
-
-def adamw_step_ref(params, grads, ms, vs, lowps, lr, beta1, beta2, eps, weight_decay, bc1, bc2, inv_scale=1.0):
-    for p, g, m, v, lp in zip(params, grads, ms, vs, lowps):
-        gf = g.float()
-        if inv_scale != 1.0:
-            gf = gf * inv_scale
-        if weight_decay:
-            p.mul_(1 - lr * weight_decay)
-        m.mul_(beta1).add_(gf, alpha=1 - beta1)
-        v.mul_(beta2).addcmul_(gf, gf, value=1 - beta2)
-        denom = (v / bc2).sqrt_().add_(eps)
-        p.addcdiv_(m, denom, value=-lr / bc1)
-        if lp is not None:
-            lp.copy_(p)
-
-
 _SQ_CACHE = {}
 
 
@@ -84,7 +43,9 @@ def global_sq_norm(tensors):
         return None
     t0 = tensors[0]
     if L.hip_enabled_for(t0) and L.has("pa_sq_norm_multi") and all(t.is_contiguous() for t in tensors):
-        key = tuple(t.data_ptr() for t in tensors)
+        # the table rows hold {ptr, numel, dtype}: all three are the key (the caching allocator hands the same
+        # address to tensors of another length or type)
+        key = tuple((t.data_ptr(), t.numel(), t.dtype) for t in tensors)
         ent = _SQ_CACHE.get(key)
         if ent is None:
             rows, items = [], []

@@ -38,6 +38,10 @@ class Adam(Optimizer):
     def _coeff_for(self, group, p):
         return 0.0
 
+    def _lr_mult(self, p):
+        """Per-parameter multiplier of the group's learning rate (ParamAttr.learning_rate)."""
+        return p.optimize_attr.get("learning_rate", 1.0) if hasattr(p, "optimize_attr") else 1.0
+
     def _apply_clip(self):
         """Global-norm clipping folded into the fused update: the clip coefficient stays a device
         scalar that the AdamW kernel multiplies into every gradient it reads (no separate pass over
@@ -90,7 +94,7 @@ class Adam(Optimizer):
             g = self._regularized_grad(p, g, group)
         m = self._acc("moment1", p)
         v = self._acc("moment2", p)
-        plr = lr * (p.optimize_attr.get("learning_rate", 1.0) if hasattr(p, "optimize_attr") else 1.0)
+        plr = lr * self._lr_mult(p)
         coeff = self._coeff_for(group, p)
         if coeff:
             w.mul_(1.0 - plr * coeff)
@@ -125,10 +129,9 @@ class Adam(Optimizer):
                 n = w.numel()
                 gdt = L._DT[g.dtype]
                 ldt = 3 if lp is None else L._DT[lp.dtype]
-                lr_mult = p.optimize_attr.get("learning_rate", 1.0) if hasattr(p, "optimize_attr") else 1.0
                 rows.append([w.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(),
                              0 if lp is None else lp.data_ptr(), n, gdt | (ldt << 8),
-                             _f2i(self._coeff_for(group, p)), _f2i(lr_mult)])
+                             _f2i(self._coeff_for(group, p)), _f2i(self._lr_mult(p))])
                 for s in range(0, n, _opt._CHUNK):
                     items.append([i, s])
             dev = fp32[0].device
@@ -259,6 +262,12 @@ class AdamW(Adam):
         if self._apply_decay_param_fun is not None and not self._apply_decay_param_fun(p.name):
             return 0.0
         return float(wd or 0.0)
+
+    def _lr_mult(self, p):
+        # layer-wise lr decay: lr_ratio(param) scales that parameter's lr in the update and in the decoupled
+        # decay 1 - lr * ratio * coeff (reference: adamw.py passes lr_ratio to the kernel, which scales lr first)
+        mult = super()._lr_mult(p)
+        return mult if self._lr_ratio is None else mult * float(self._lr_ratio(p))
 
     def _group_lr(self, group, param=None):
         return super()._group_lr(group, None)

@@ -142,6 +142,47 @@ def test_adamw_matches_torch_reference():
         np.testing.assert_allclose(p.numpy(), r.detach().numpy(), rtol=1e-5, atol=1e-6)
 
 
+def test_adamw_lr_ratio_scales_update_and_decay():
+    """AdamW(lr_ratio=f): f(param) multiplies that parameter's lr in the update and in the decoupled decay
+    (float64 reference of p*(1 - lr*r*wd) - lr*r/bc1 * m/(sqrt(v/bc2) + eps)); ratio 0 freezes the parameter
+    while its moments still advance."""
+    torch.manual_seed(4)
+    lr, b1, b2, eps, wd = 0.01, 0.8, 0.95, 1e-6, 0.1
+    ratios = {"frozen": 0.0, "half": 0.5, "full": 1.0}
+    ws = {k: torch.randn(5, 3) for k in ratios}
+    ps = [paddle.Parameter(w.clone(), name=k) for k, w in ws.items()]
+    seen = []
+
+    def ratio(p):
+        seen.append(p)
+        return ratios[p.name]
+
+    opt = paddle.optimizer.AdamW(lr, beta1=b1, beta2=b2, epsilon=eps, parameters=ps, weight_decay=wd, lr_ratio=ratio)
+    ref = {k: [w.double(), torch.zeros(5, 3, dtype=torch.float64), torch.zeros(5, 3, dtype=torch.float64)]
+           for k, w in ws.items()}
+    for t in range(1, 4):
+        for p in ps:
+            g = torch.randn(5, 3)
+            p._t.grad = g.clone()
+            w, m, v = ref[p.name]
+            r = ratios[p.name]
+            m = b1 * m + (1 - b1) * g.double()
+            v = b2 * v + (1 - b2) * g.double() ** 2
+            w = w * (1 - lr * r * wd) - lr * r / (1 - b1 ** t) * m / ((v / (1 - b2 ** t)).sqrt() + eps)
+            ref[p.name] = [w, m, v]
+        opt.step()
+    assert seen and all(isinstance(p, paddle.Parameter) for p in seen)  # the callable receives the parameter
+    for p in ps:
+        w, m, v = ref[p.name]
+        np.testing.assert_allclose(p.numpy(), w.numpy(), rtol=1e-5, atol=1e-6)
+        np.testing.assert_allclose(opt._accumulators["moment1"][id(p)].numpy(), m.numpy(), rtol=1e-5, atol=1e-7)
+        np.testing.assert_allclose(opt._accumulators["moment2"][id(p)].numpy(), v.numpy(), rtol=1e-5, atol=1e-7)
+    assert torch.equal(ps[0]._t.detach(), ws["frozen"])  # ratio 0: bit-identical
+    assert float(opt._accumulators["moment2"][id(ps[0])].min()) > 0.0  # ... while the moments advanced
+    moved = {p.name: (p._t.detach() - ws[p.name]).abs().max().item() for p in ps}
+    assert moved["half"] > 1e-3 and moved["full"] > 1e-3
+
+
 def test_optimizer_state_dict_roundtrip(tmp_path):
     m = paddle.nn.Linear(4, 4)
     opt = paddle.optimizer.Adam(0.1, parameters=m.parameters())
