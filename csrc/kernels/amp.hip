@@ -1,42 +1,22 @@
 // Multi-tensor non-finite check + unscale of gradients (loss scaling) for gfx950.
 // Reference behaviour: paddle/phi/kernels/gpu/amp_kernel.cu (check_finite_and_unscale).
 //
-// Same device table / work-item layout as sq_norm_multi_k (adamw.hip):
-//   table rows (3 x int64): [ptr, numel, dtype]; work items (2 x int64): [tensor index, start element];
-//   each item covers kChunk elements. A persistent grid walks the items.
+// Table rows (TensorRow) and work items of multi_tensor.h, as in sq_norm_multi_k (adamw.hip).
 // Per element: x loaded as fp32, y = x * *inv_scale stored back in the tensor's own dtype. One launch covers
 // fp32 / bf16 / fp16 tensors together. found_inf[0] is set to 1 when any loaded value is inf or nan; it is never
 // cleared here, so calls accumulate.
-#include "common.h"
+#include "multi_tensor.h"
 
 using namespace pa;
 
 namespace {
 
-constexpr int64_t kChunk = 16384;
 constexpr int kUnroll = 4;  // 16-byte requests in flight per lane in the vector body
 
 // exponent all ones, tested on the bits: holds whatever floating-point flags the file is built with
 __device__ __forceinline__ int non_finite(float x) {
   return (__float_as_uint(x) & 0x7f800000u) == 0x7f800000u;
 }
-
-// one 16-byte access per lane: 4 x fp32 or 8 x bf16 / fp16
-template <typename T> struct V16 {
-  static constexpr int kPer = 8;
-  static __device__ __forceinline__ void ld(const T* p, float* f) { load8<T>(p, f); }
-  static __device__ __forceinline__ void st(T* p, const float* f) { store8<T>(p, f); }
-};
-template <> struct V16<float> {
-  static constexpr int kPer = 4;
-  static __device__ __forceinline__ void ld(const float* p, float* f) {
-    const float4 v = *reinterpret_cast<const float4*>(p);
-    f[0] = v.x; f[1] = v.y; f[2] = v.z; f[3] = v.w;
-  }
-  static __device__ __forceinline__ void st(float* p, const float* f) {
-    *reinterpret_cast<float4*>(p) = make_float4(f[0], f[1], f[2], f[3]);
-  }
-};
 
 // elements [s, e) of X in place; returns 1 if this thread loaded a non-finite value
 template <typename T>
@@ -90,15 +70,17 @@ __global__ __launch_bounds__(256) void amp_check_unscale_multi_k(const int64_t* 
                                                                  float* __restrict__ found_inf) {
   const float inv = *inv_scale;
   int bad = 0;
+  // for_each_item<TensorRow> written out: through its lambda the compiler lays this kernel out differently (17 more
+  // instructions), and that code did not stay inside the parent's timing spread in every run
   for (int64_t it = blockIdx.x; it < n_items; it += gridDim.x) {
     const int64_t ti = items[it * 2], s = items[it * 2 + 1];
-    void* X = (void*)table[ti * 3];
-    const int64_t n = table[ti * 3 + 1];
-    const int dt = (int)table[ti * 3 + 2];
+    const int64_t* row = table + ti * TensorRow::kCols;
+    const TensorRow r(row);
+    const int64_t n = row[TensorRow::kNumelCol];
     const int64_t e = s + kChunk < n ? s + kChunk : n;
-    if (dt == kF32) bad |= unscale_item<float>((float*)X, s, e, inv);
-    else if (dt == kBF16) bad |= unscale_item<bf16>((bf16*)X, s, e, inv);
-    else if (dt == kF16) bad |= unscale_item<f16>((f16*)X, s, e, inv);
+    if (r.dt == kF32) bad |= unscale_item<float>((float*)r.x, s, e, inv);
+    else if (r.dt == kBF16) bad |= unscale_item<bf16>((bf16*)r.x, s, e, inv);
+    else if (r.dt == kF16) bad |= unscale_item<f16>((f16*)r.x, s, e, inv);
   }
   // every writer stores the same value: no atomic needed
   if (__syncthreads_or(bad) && threadIdx.x == 0) found_inf[0] = 1.0f;
@@ -110,9 +92,8 @@ __global__ __launch_bounds__(256) void amp_check_unscale_multi_k(const int64_t* 
 PA_EXPORT int pa_amp_check_unscale_multi(const int64_t* table, const int64_t* items, int64_t n_items,
                                          const float* inv_scale, float* found_inf, hipStream_t st) {
   if (n_items <= 0) return 0;
-  const int64_t g = n_items < 1024 ? n_items : 1024;
-  hipLaunchKernelGGL(amp_check_unscale_multi_k, dim3((unsigned)g), dim3(256), 0, st, table, items, n_items, inv_scale,
-                     found_inf);
+  hipLaunchKernelGGL(amp_check_unscale_multi_k, dim3(mt_grid(n_items, 1024)), dim3(256), 0, st, table, items,
+                     n_items, inv_scale, found_inf);
   PA_CHECK_LAUNCH();
   return 0;
 }

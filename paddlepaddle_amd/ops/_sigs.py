@@ -44,6 +44,7 @@ SIGS = {
     "pa_write_i64": [_vp, _vp, _i64, _vp],
     "pa_bn_set_target_wgs": [_i32],
     "pa_momentum_multi": [_vp, _vp, _i64, _vp, _f32, _f32, _f32, _i32, _vp],
+    "pa_multi_tensor_chunk": [],
     # loss scaling (csrc/kernels/amp.hip)
     "pa_amp_check_unscale_multi": [_vp, _vp, _i64, _vp, _vp, _vp],
     # attention
@@ -142,4 +143,4 @@ SIGS = {
 }
 
 RET_I64 = {"pa_flash_attn_bwd_ds_bytes", "pa_gemm_pp_ws_bytes", "pa_gemm_fp8_ws_bytes", "pa_gemm_pp_splitk_ws_bytes", "pa_bn_pre_ws", "pa_gemm_skinny_stats_chunks", "pa_conv_skinny_stats_chunks",
-           "pa_colsum_nparts"}
+           "pa_colsum_nparts", "pa_multi_tensor_chunk"}

@@ -2,34 +2,16 @@
 
 Reference: paddle/phi/kernels/gpu/amp_kernel.cu (check_finite_and_unscale), python/paddle/amp/grad_scaler.py:315.
 Kernel: csrc/kernels/amp.hip — one launch covers every tensor of every dtype (fp32 / bf16 / fp16) through the same
-device table + 16384-element work items as the multi-tensor sum of squares (ops/optim.py).
+device table + work items as the multi-tensor sum of squares (ops/multi_tensor.py, ops/optim.py).
 """
 from __future__ import annotations
 
 import torch
 
 from . import _loader as L
-from .optim import _CHUNK, device_table
+from . import multi_tensor as MT
 
 _TABLE_CACHE = {}
-
-
-def _tables(tensors, dev):
-    key = (dev,) + tuple((t.data_ptr(), t.numel(), L._DT[t.dtype]) for t in tensors)
-    ent = _TABLE_CACHE.get(key)
-    if ent is None:
-        rows, items = [], []
-        for i, t in enumerate(tensors):
-            rows.append([t.data_ptr(), t.numel(), L._DT[t.dtype]])
-            for s in range(0, t.numel(), _CHUNK):
-                items.append([i, s])
-        table, table_host = device_table(rows, dev)
-        work, work_host = device_table(items, dev)
-        ent = (table, work, len(items), table_host, work_host)  # host twins stay alive behind the async copies
-        if len(_TABLE_CACHE) > 64:
-            _TABLE_CACHE.clear()
-        _TABLE_CACHE[key] = ent
-    return ent
 
 
 def _unscale_ref(tensors, inv_scale, found_inf):
@@ -53,8 +35,8 @@ def check_finite_and_unscale_(tensors, inv_scale, found_inf):
         live = [t for t in tensors if t.numel() > 0]
         if not live:
             return
-        table, work, n, _, _ = _tables(live, t0.device)
-        L.call("pa_amp_check_unscale_multi", L.ptr(table), L.ptr(work), n, L.ptr(inv_scale), L.ptr(found_inf),
-               L.stream_ptr())
+        ent = MT.cached_tables(_TABLE_CACHE, None, MT.tensor_keys(live), t0.device)
+        L.call("pa_amp_check_unscale_multi", L.ptr(ent.table), L.ptr(ent.items), ent.n_items, L.ptr(inv_scale),
+               L.ptr(found_inf), L.stream_ptr())
         return
     _unscale_ref(tensors, inv_scale, found_inf)

@@ -7,19 +7,12 @@ the device table.
 """
 from __future__ import annotations
 
-import struct
-
 import torch
 
 from .lr import LRScheduler
 
 from ..ops import _loader as L
-from ..ops import optim as _opt
 from .optimizer import Optimizer
-
-
-def _f2i(x):
-    return struct.unpack("<i", struct.pack("<f", float(x)))[0]
 
 
 class Adam(Optimizer):
@@ -32,15 +25,10 @@ class Adam(Optimizer):
         super().__init__(learning_rate, parameters, weight_decay, grad_clip, name, multi_precision)
         self._beta1, self._beta2, self._epsilon = beta1, beta2, epsilon
         self._amsgrad = amsgrad
-        self._tables = {}
         self._param_step = {}
 
     def _coeff_for(self, group, p):
         return 0.0
-
-    def _lr_mult(self, p):
-        """Per-parameter multiplier of the group's learning rate (ParamAttr.learning_rate)."""
-        return p.optimize_attr.get("learning_rate", 1.0) if hasattr(p, "optimize_attr") else 1.0
 
     def _apply_clip(self):
         """Global-norm clipping folded into the fused update: the clip coefficient stays a device
@@ -115,33 +103,8 @@ class Adam(Optimizer):
         self._acc("beta2_pow_acc", p, shape=[1]).fill_(b2 ** step)
 
     def _fused(self, group, params, lr, b1, b2, eps, step):
-        masters = [self._master(p) for p in params]
-        fp32 = [m if m is not None else p._t.detach() for p, m in zip(params, masters)]
-        grads = [p._t.grad for p in params]
-        key = (id(group), tuple(t.data_ptr() for t in fp32), tuple(g.data_ptr() for g in grads))
-        tab = self._tables.get(id(group))
-        if tab is None or tab[0] != key:
-            ms = [self._acc("moment1", p) for p in params]
-            vs = [self._acc("moment2", p) for p in params]
-            lowps = [p._t.detach() if m is not None else None for p, m in zip(params, masters)]
-            rows, items = [], []
-            for i, (w, g, m, v, lp, p) in enumerate(zip(fp32, grads, ms, vs, lowps, params)):
-                n = w.numel()
-                gdt = L._DT[g.dtype]
-                ldt = 3 if lp is None else L._DT[lp.dtype]
-                rows.append([w.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(),
-                             0 if lp is None else lp.data_ptr(), n, gdt | (ldt << 8),
-                             _f2i(self._coeff_for(group, p)), _f2i(self._lr_mult(p))])
-                for s in range(0, n, _opt._CHUNK):
-                    items.append([i, s])
-            dev = fp32[0].device
-            t_rows, h_rows = _opt.device_table(rows, dev)
-            t_items, h_items = _opt.device_table(items, dev)
-            tab = (key, t_rows, t_items, len(items), fp32, grads, (h_rows, h_items))
-            self._tables[id(group)] = tab
-            if torch.cuda.is_available() and torch.cuda.is_current_stream_capturing():
-                self.__dict__.setdefault("_graph_hosts", []).append(tab[6])  # read by every replay
-        _, t_rows, t_items, n_items = tab[:4]
+        tab = self._group_tables(group, params, ("moment1", "moment2"), lambda p: self._coeff_for(group, p))
+        w0 = tab.extra[0]
         bc1 = 1 - b1 ** step
         bc2 = 1 - b2 ** step
         inv_scale = getattr(self, "_inv_scale_tensor", None)
@@ -149,16 +112,16 @@ class Adam(Optimizer):
         if coef is not None:
             inv_scale = coef if inv_scale is None else (coef * inv_scale.reshape(())).reshape(())
         hyper = None
-        if fp32[0].is_cuda:
+        if w0.is_cuda:
             # the device copy of {lr, beta1^t, beta2^t} is created on the first (eager) step and advanced by every
             # step, so a step captured later into a hipGraph starts from the right powers; eager steps still pass
             # host floats, captured ones read the device copy
-            h = self._graph_hyper(group, fp32[0].device, lr, b1, b2, step)
+            h = self._graph_hyper(group, w0.device, lr, b1, b2, step)
             L.call("pa_adam_hyper_step", L.ptr(h), float(b1), float(b2), L.stream_ptr())
             if torch.cuda.is_current_stream_capturing():
                 hyper = h
-        L.call("pa_adamw_multi", L.ptr(t_rows), L.ptr(t_items), n_items, L.ptr(inv_scale), float(lr), float(b1),
-               float(b2), float(eps), 0.0, float(bc1), float(bc2), L.ptr(hyper), L.stream_ptr())
+        L.call("pa_adamw_multi", L.ptr(tab.table), L.ptr(tab.items), tab.n_items, L.ptr(inv_scale), float(lr),
+               float(b1), float(b2), float(eps), 0.0, float(bc1), float(bc2), L.ptr(hyper), L.stream_ptr())
         self._last_step = step
 
     def _graph_hyper(self, group, dev, lr, b1, b2, step):

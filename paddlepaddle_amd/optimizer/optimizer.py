@@ -62,6 +62,7 @@ class Optimizer:
         self._multi_precision = multi_precision
         self._accumulators = collections.defaultdict(dict)  # acc name -> {param id: tensor}
         self._master_weights = {}
+        self._tables = {}  # id(param group) -> device tables of its fused multi-tensor launch (_group_tables)
         self._step_count = 0
         self._name = name
         self.helper = None
@@ -115,6 +116,34 @@ class Optimizer:
         if k not in self._master_weights:
             self._master_weights[k] = t.detach().float().clone()
         return self._master_weights[k]
+
+    def _lr_mult(self, p):
+        """Per-parameter multiplier of the group's learning rate (ParamAttr.learning_rate)."""
+        return p.optimize_attr.get("learning_rate", 1.0) if hasattr(p, "optimize_attr") else 1.0
+
+    def _group_tables(self, group, params, states, wd_of):
+        """Device tables (ops.multi_tensor.Tables) of a group's fused multi-tensor update, rebuilt when a pointer,
+        length or dtype in its rows changes. Row of a parameter: [fp32 weight (the master if there is one), grad,
+        the ``states`` accumulators (two columns), low-precision shadow or 0, numel, grad dtype | shadow dtype << 8,
+        ``wd_of(p)``, lr multiplier]. ``extra`` of the entry holds the weights and gradients the rows point at."""
+        from ..ops import _loader as L
+        from ..ops import multi_tensor as MT
+        keys, keep = [], []
+        for p in params:
+            master = self._master(p)
+            w, g = master if master is not None else p._t.detach(), p._t.grad
+            ldt = MT.NO_SHADOW if master is None else L._DT[p._t.dtype]
+            st = [self._acc(name, p).data_ptr() for name in states] + [0] * (2 - len(states))
+            keys.append((w.data_ptr(), g.data_ptr(), *st, 0 if master is None else p._t.data_ptr(), w.numel(),
+                         L._DT[g.dtype] | (ldt << 8)))
+            keep += [w, g]
+        old = self._tables.get(id(group))
+        tab = MT.cached_tables(
+            self._tables, id(group), keys, keep[0].device, extra=lambda: keep,
+            scalars=lambda: [(MT.f32_bits(wd_of(p)), MT.f32_bits(self._lr_mult(p))) for p in params])
+        if tab is not old and torch.cuda.is_available() and torch.cuda.is_current_stream_capturing():
+            self.__dict__.setdefault("_graph_hosts", []).append(tab.hosts)  # read by every replay
+        return tab
 
     def state_dict(self):
         sd = collections.OrderedDict()

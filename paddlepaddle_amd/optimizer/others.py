@@ -80,37 +80,11 @@ class Momentum(_HostLrCapture, _PerParam):
 
     def _fused(self, group, params):
         from ..ops import _loader as L
-        from ..ops import optim as _opt
-        from .adam import _f2i
-        masters = [self._master(p) for p in params]
-        fp32 = [m if m is not None else p._t.detach() for p, m in zip(params, masters)]
-        grads = [p._t.grad for p in params]
-        key = (tuple(t.data_ptr() for t in fp32), tuple(g.data_ptr() for g in grads))
-        tabs = self.__dict__.setdefault("_mt_tables", {})
-        tab = tabs.get(id(group))
-        if tab is None or tab[0] != key:
-            rows, items = [], []
-            for i, (w, g, m, p) in enumerate(zip(fp32, grads, masters, params)):
-                vel = self._acc("velocity", p)
-                reg = self._regularizer_for(p, group)
-                lr_mult = p.optimize_attr.get("learning_rate", 1.0) if hasattr(p, "optimize_attr") else 1.0
-                ldt = 3 if m is None else L._DT[p._t.dtype]
-                rows.append([w.data_ptr(), g.data_ptr(), vel.data_ptr(), 0, 0 if m is None else p._t.data_ptr(),
-                             w.numel(), L._DT[g.dtype] | (ldt << 8), _f2i(reg._coeff if reg is not None else 0.0),
-                             _f2i(lr_mult)])
-                for s0 in range(0, w.numel(), _opt._CHUNK):
-                    items.append([i, s0])
-            dev = fp32[0].device
-            t_rows, h_rows = _opt.device_table(rows, dev)
-            t_items, h_items = _opt.device_table(items, dev)
-            tab = (key, t_rows, t_items, len(items), fp32, grads, (h_rows, h_items))
-            tabs[id(group)] = tab
-            if torch.cuda.is_available() and torch.cuda.is_current_stream_capturing():
-                self.__dict__.setdefault("_graph_hosts", []).append(tab[6])  # read by every replay
-        _, t_rows, t_items, n_items = tab[:4]
+        tab = self._group_tables(group, params, ("velocity",),  # wd column: the L2 coefficient, 0 without a regularizer
+                                 lambda p: getattr(self._regularizer_for(p, group), "_coeff", 0.0))
         lr = self._group_lr(group, None)
         mu = group.get("momentum", self._momentum)
-        L.call("pa_momentum_multi", L.ptr(t_rows), L.ptr(t_items), n_items,
+        L.call("pa_momentum_multi", L.ptr(tab.table), L.ptr(tab.items), tab.n_items,
                L.ptr(getattr(self, "_inv_scale_tensor", None)), float(lr), float(mu), float(self._rescale),
                int(bool(self._nesterov)), L.stream_ptr())
 

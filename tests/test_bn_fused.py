@@ -124,7 +124,7 @@ def test_momentum_multi_tensor_hip_matches_fp32(nesterov):
             gj = g.bfloat16().float() + 1e-2 * masters[i]
             vel[i] = 0.9 * vel[i] + gj
             masters[i] = masters[i] - 0.1 * (gj + 0.9 * vel[i] if nesterov else vel[i])
-    assert getattr(opt, "_mt_tables", None), "fused multi-tensor path not taken"
+    assert opt._tables, "fused multi-tensor path not taken"
     from paddlepaddle_amd.ops import _loader as L
     assert L.calls("pa_momentum_multi") == 3
     for p, m in zip(params, masters):

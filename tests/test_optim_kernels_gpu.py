@@ -270,7 +270,7 @@ def test_adamw_grid_wrap_4100_items():
         _check("adamw.p", f"flat step {t}", flat_p, eag[0], ref[0], TOL_ADAMW_P)
         _check("adamw.m", f"flat step {t}", m1, eag[1], ref[1], TOL_ADAMW_M)
         _check("adamw.v", f"flat step {t}", m2, eag[2], ref[2], RTOL_ADAMW_V, err=_rel_err)
-    assert opt._tables[id(opt._param_groups[0])][3] == n_p  # work items
+    assert opt._tables[id(opt._param_groups[0])].n_items == n_p  # work items
     _report("adamw.p", "adamw.m", "adamw.v")
 
 
@@ -303,6 +303,51 @@ def test_adamw_lr_ratio_gpu():
     _run_adamw(opt, ents, wd_of=lambda name: 0.1, ratio_of=ratios.get, seed0=5000, after_step=frozen)
     assert seen and all(isinstance(p, paddle.Parameter) for p in seen)  # the callable receives the parameter
     assert float(opt._accumulators["moment2"][id(ents[0].param)].min()) > 0.0
+
+
+def test_adamw_table_follows_a_replaced_moment():
+    """The group's device table is keyed on every pointer in its rows: a ``moment1`` accumulator replaced by a fresh
+    tensor of ones (new address; parameter and gradient addresses unchanged) is the one the next step reads and
+    writes, and the orphaned tensor is left alone. With N(0, 1) gradients the step-2 parameter computed from the
+    orphaned moment is 4e-2 of max|p| (7 elements) away from the one computed from the ones, 4e4 x ``TOL_ADAMW_P``
+    (float64 on the CPU, median over seeds 0..99; smallest 1.0e-2, largest 0.2). A table keyed on the parameter
+    and gradient pointers alone fails the parameter, the moment and the orphan check."""
+    lr, wd, b1, b2, eps = 1e-2, 0.1, 0.8, 0.95, 1e-6
+    ents = [_Ent("s0", (7,), F32, 800), _Ent("s1", (CHUNK + 1,), F32, 801)]
+    opt = paddle.optimizer.AdamW(lr, beta1=b1, beta2=b2, epsilon=eps, parameters=[e.param for e in ents],
+                                 weight_decay=wd)
+    ref = {e.name: e.state(F64) for e in ents}
+
+    def step(t):
+        for i, e in enumerate(ents):
+            e.new_grad(8000 + 100 * t + i, 1.0)
+        opt.step()
+
+    step(1)
+    for e in ents:
+        ref[e.name] = _adamw_math(ref[e.name], e.grad.double(), lr, 1.0, wd, b1, b2, eps, 1)
+    m1 = opt._accumulators["moment1"]
+    old = m1[id(ents[0].param)]
+    fresh = torch.ones(7, dtype=F32, device="cuda")
+    assert fresh.data_ptr() != old.data_ptr()
+    m1[id(ents[0].param)] = fresh
+    old_bits = _bits(old).clone()
+    ptrs = [(e.param._t.data_ptr(), e.grad.data_ptr()) for e in ents]
+
+    step(2)
+    assert ptrs == [(e.param._t.data_ptr(), e.param._t.grad.data_ptr()) for e in ents]
+    orphan = _adamw_math(ref["s0"], ents[0].grad.double(), lr, 1.0, wd, b1, b2, eps, 2)
+    ref["s0"][1] = torch.ones(7, dtype=F64, device="cuda")
+    for e in ents:
+        ref[e.name] = _adamw_math(ref[e.name], e.grad.double(), lr, 1.0, wd, b1, b2, eps, 2)
+        assert _scaled_err(e.param._t.detach(), ref[e.name][0]) <= TOL_ADAMW_P, e.name
+        assert _scaled_err(m1[id(e.param)], ref[e.name][1]) <= TOL_ADAMW_M, e.name
+    assert _scaled_err(orphan[0], ref["s0"][0]) > 1000 * TOL_ADAMW_P  # the check above tells the two tables apart
+    assert m1[id(ents[0].param)] is fresh and not bool((fresh == 1).all()), "the new moment was not written"
+    assert torch.equal(_bits(old), old_bits), "the orphaned moment was written"
+
+    from paddlepaddle_amd.ops import multi_tensor as MT
+    assert L.lib().pa_multi_tensor_chunk() == MT.CHUNK == CHUNK
 
 
 # ------------------------------------------------------------------------------------------------------- Momentum
