@@ -44,16 +44,25 @@ template <int kStates> struct UpdateRow {
   }
 };
 
-// body(row, s, e) for every item of this workgroup: elements [s, e) of the tensor that `row` describes
+// body(row, s, e, it, ti) for every item of this workgroup: elements [s, e) of the tensor that `row` describes, item
+// number `it` of the work list, tensor number `ti` of the table
 template <typename Row, typename Body>
-__device__ __forceinline__ void for_each_item(const int64_t* table, const int64_t* items, int64_t n_items,
-                                              Body&& body) {
+__device__ __forceinline__ void for_each_item_at(const int64_t* table, const int64_t* items, int64_t n_items,
+                                                 Body&& body) {
   for (int64_t it = blockIdx.x; it < n_items; it += gridDim.x) {
     const int64_t ti = items[it * 2], s = items[it * 2 + 1];
     const int64_t* r = table + ti * Row::kCols;
     const int64_t n = r[Row::kNumelCol];
-    body(Row(r), s, s + kChunk < n ? s + kChunk : n);
+    body(Row(r), s, s + kChunk < n ? s + kChunk : n, it, ti);
   }
+}
+
+// body(row, s, e): the same walk for a body that needs neither number
+template <typename Row, typename Body>
+__device__ __forceinline__ void for_each_item(const int64_t* table, const int64_t* items, int64_t n_items,
+                                              Body&& body) {
+  for_each_item_at<Row>(table, items, n_items,
+                        [&](const Row& r, int64_t s, int64_t e, int64_t, int64_t) { body(r, s, e); });
 }
 
 __device__ __forceinline__ float ld_any(const void* p, int64_t i, int dt) {

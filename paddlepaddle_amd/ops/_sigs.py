@@ -45,6 +45,7 @@ SIGS = {
     "pa_bn_set_target_wgs": [_i32],
     "pa_momentum_multi": [_vp, _vp, _i64, _vp, _f32, _f32, _f32, _i32, _vp],
     "pa_multi_tensor_chunk": [],
+    "pa_lamb_multi": [_vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _f32, _f32, _f32, _f32, _f32, _f32, _i32, _vp],
     # loss scaling (csrc/kernels/amp.hip)
     "pa_amp_check_unscale_multi": [_vp, _vp, _i64, _vp, _vp, _vp],
     # attention

@@ -1,11 +1,12 @@
 """Host side of the multi-tensor launches (csrc/kernels/multi_tensor.h): device tables, work items and their cache.
 
-A multi-tensor kernel (AdamW / Momentum update, sum of squares, loss-scaling unscale) takes a device table of int64
-rows, one per tensor, and ``[tensor index, start element]`` work items, one per ``CHUNK`` elements. A row starts with
-its key columns: every pointer the kernel follows, then the element count and the dtype word. Scalar columns (weight
-decay, lr multiplier) follow. ``cached_tables`` keeps the uploaded tables until a key column changes: optimizers hold
-one entry per parameter group, module-level users (norm, unscale) up to 64 in a dict of their own. A module-level
-entry built while a hipGraph is being captured is written by captured kernels: only a replay of that graph fills it.
+A multi-tensor kernel (AdamW / Momentum / LAMB update, sum of squares, loss-scaling unscale) takes a device table of
+int64 rows, one per tensor, and ``[tensor index, start element]`` work items, one per ``CHUNK`` elements. A row starts
+with its key columns: every pointer the kernel follows, then the element count and the dtype word. Scalar columns
+(weight decay, lr multiplier) follow. ``cached_tables`` keeps the uploaded tables until a key column changes:
+optimizers hold one entry per parameter group, module-level users (norm, unscale) up to 64 in a dict of their own. A
+module-level entry built while a hipGraph is being captured is written by captured kernels: only a replay of that graph
+fills it.
 """
 from __future__ import annotations
 
@@ -43,14 +44,22 @@ def device_table(rows, dev):
     return host.to(dev, non_blocking=True), host
 
 
+def item_offsets(numels):
+    """int64 ``[n + 1]``: tensor ``i`` of a launch over ``numels`` owns the work items ``[off[i], off[i + 1])``,
+    ``ceil(numel / CHUNK)`` of them (none for an empty tensor). What a per-tensor reduction over item partials
+    (csrc/kernels/lamb.hip) walks."""
+    per = (torch.tensor(numels, dtype=torch.int64) + (CHUNK - 1)) // CHUNK
+    return torch.cat([torch.zeros(1, dtype=torch.int64), torch.cumsum(per, 0)])
+
+
 def build_tables(rows, numels, dev):
     """``(table, items, n_items, hosts)`` of one launch: ``rows`` on ``dev`` ([n, cols]), the [n_items, 2] work list
-    in tensor order (``ceil(numel / CHUNK)`` items per tensor, none for an empty one) and the host twins, which must
-    outlive the asynchronous copies."""
+    in tensor order (the items of ``item_offsets``) and the host twins, which must outlive the asynchronous
+    copies."""
     table, table_host = device_table(rows, dev)
-    per = (torch.tensor(numels, dtype=torch.int64) + (CHUNK - 1)) // CHUNK
-    index = torch.repeat_interleave(torch.arange(len(numels)), per)
-    first = torch.cumsum(per, 0) - per  # position of each tensor's first item
+    off = item_offsets(numels)
+    first = off[:-1]  # position of each tensor's first item
+    index = torch.repeat_interleave(torch.arange(len(numels)), off[1:] - first)
     start = (torch.arange(index.numel()) - first[index]) * CHUNK
     items, items_host = device_table(torch.stack([index, start], 1), dev)
     return table, items, index.numel(), (table_host, items_host)

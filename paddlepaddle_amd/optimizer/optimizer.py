@@ -121,11 +121,12 @@ class Optimizer:
         """Per-parameter multiplier of the group's learning rate (ParamAttr.learning_rate)."""
         return p.optimize_attr.get("learning_rate", 1.0) if hasattr(p, "optimize_attr") else 1.0
 
-    def _group_tables(self, group, params, states, wd_of):
+    def _group_tables(self, group, params, states, wd_of, more=None):
         """Device tables (ops.multi_tensor.Tables) of a group's fused multi-tensor update, rebuilt when a pointer,
         length or dtype in its rows changes. Row of a parameter: [fp32 weight (the master if there is one), grad,
         the ``states`` accumulators (two columns), low-precision shadow or 0, numel, grad dtype | shadow dtype << 8,
-        ``wd_of(p)``, lr multiplier]. ``extra`` of the entry holds the weights and gradients the rows point at."""
+        ``wd_of(p)``, lr multiplier]. ``extra`` of the entry holds the weights and gradients the rows point at and,
+        last, ``more(numels, device)`` where the update keeps buffers of its own with the table."""
         from ..ops import _loader as L
         from ..ops import multi_tensor as MT
         keys, keep = [], []
@@ -139,7 +140,8 @@ class Optimizer:
             keep += [w, g]
         old = self._tables.get(id(group))
         tab = MT.cached_tables(
-            self._tables, id(group), keys, keep[0].device, extra=lambda: keep,
+            self._tables, id(group), keys, keep[0].device,
+            extra=lambda: keep if more is None else keep + [more([k[-2] for k in keys], keep[0].device)],
             scalars=lambda: [(MT.f32_bits(wd_of(p)), MT.f32_bits(self._lr_mult(p))) for p in params])
         if tab is not old and torch.cuda.is_available() and torch.cuda.is_current_stream_capturing():
             self.__dict__.setdefault("_graph_hosts", []).append(tab.hosts)  # read by every replay

@@ -3,6 +3,7 @@ Reference: python/paddle/optimizer/{sgd,momentum,adamax,adagrad,adadelta,rmsprop
 rprop,lbfgs}.py."""
 from __future__ import annotations
 
+import collections
 import math
 
 import torch
@@ -180,7 +181,21 @@ class RMSProp(_PerParam):
         self._fin(p, master)
 
 
+LambBuffers = collections.namedtuple("LambBuffers", "offsets partial trust hosts")
+
+
 class Lamb(_PerParam):
+    """LAMB. On a HIP device the fp32 (or fp32-master) parameters of a group that no regularizer applies to are updated
+    by one ``pa_lamb_multi`` call (csrc/kernels/lamb.hip): moments and per-item norm partials, one trust ratio per
+    tensor, then the parameter and its low-precision shadow. Everything else takes ``_update_param``, one parameter at
+    a time. The buffers of the fused update live with the group's table entry: after a step
+    ``opt._tables[id(group)].extra[-1]`` is a ``LambBuffers`` whose ``trust[i]`` is the trust ratio just applied to
+    the group's ``i``-th fused parameter (1 where the row does not adapt).
+
+    Not covered by the fused path: hipGraph capture of a step (``_graph_capturable`` stays False: the bias corrections
+    are host floats), a global-norm clip folded into the kernel (the clip runs before, as a pass of its own), norms
+    across sharded or tensor-parallel shards (each rank's norms are over what it holds), the native training executor
+    (csrc/interpreter/train_interp.cpp) and LARS."""
     _acc_names = ("moment1", "moment2", "beta1_pow_acc", "beta2_pow_acc")
 
     def __init__(self, learning_rate=0.001, lamb_weight_decay=0.01, beta1=0.9, beta2=0.999, epsilon=1e-06,
@@ -190,9 +205,55 @@ class Lamb(_PerParam):
         self._wd, self._b1, self._b2, self._eps = lamb_weight_decay, beta1, beta2, epsilon
         self._exclude = exclude_from_weight_decay_fn
         self._always_adapt = always_adapt
+        self._param_step = {}  # id(param) -> updates applied so far, by either path
+
+    def _decay_for(self, p):
+        return 0.0 if (self._exclude is not None and self._exclude(p)) else self._wd
+
+    def _update_group(self, group, params):
+        from ..ops import _loader as L
+        fused = []
+        if L.hip_enabled_for(params[0]._t) and L.has("pa_lamb_multi"):
+            fused = [p for p in params
+                     if (p._t.dtype == torch.float32 or self._multi_precision) and p._t.grad.dtype in L._DT
+                     and self._regularizer_for(p, group) is None]
+            if len({self._param_step.get(id(p), 0) for p in fused}) > 1:
+                fused = []  # one bias correction per launch
+        if fused:
+            self._fused(group, fused)
+        taken = {id(p) for p in fused}
+        for p in params:
+            if id(p) not in taken:
+                self._update_param(group, p)
+
+    def _fused(self, group, params):
+        from ..ops import _loader as L
+        from ..ops import multi_tensor as MT
+
+        def buffers(numels, dev):
+            off = MT.item_offsets(numels)
+            offsets, host = MT.device_table(off, dev)
+            return LambBuffers(offsets, torch.empty(2 * int(off[-1]), dtype=torch.float32, device=dev),
+                               torch.empty(len(numels), dtype=torch.float32, device=dev), host)
+
+        tab = self._group_tables(group, params, ("moment1", "moment2"), self._decay_for, more=buffers)
+        buf = tab.extra[-1]
+        step = self._param_step.get(id(params[0]), 0) + 1
+        for p in params:
+            self._param_step[id(p)] = step
+        torch._foreach_mul_([self._acc("beta1_pow_acc", p, init=1.0, shape=[1]) for p in params], self._b1)
+        torch._foreach_mul_([self._acc("beta2_pow_acc", p, init=1.0, shape=[1]) for p in params], self._b2)
+        # the kernel holds the betas as fp32, so the bias corrections are powers of those (as beta*_pow_acc are on the
+        # per-parameter path): with the exact betas the moments' (1 - beta) would not cancel against 1 - beta^t
+        b1, b2 = (float(torch.tensor(b, dtype=torch.float32)) for b in (self._b1, self._b2))
+        L.call("pa_lamb_multi", L.ptr(tab.table), L.ptr(tab.items), tab.n_items, L.ptr(buf.offsets), len(params),
+               L.ptr(buf.partial), L.ptr(buf.trust), L.ptr(getattr(self, "_inv_scale_tensor", None)),
+               float(self._group_lr(group, None)), b1, b2, float(self._eps), 1 - b1 ** step, 1 - b2 ** step,
+               int(bool(self._always_adapt)), L.stream_ptr())
 
     def _update_param(self, group, p):
         master, w, g, lr = self._prep(group, p)
+        self._param_step[id(p)] = self._param_step.get(id(p), 0) + 1
         m = self._acc("moment1", p)
         v = self._acc("moment2", p)
         b1p = self._acc("beta1_pow_acc", p, init=1.0, shape=[1])
@@ -203,7 +264,7 @@ class Lamb(_PerParam):
         v.mul_(self._b2).addcmul_(g, g, value=1 - self._b2)
         mh = m / (1 - b1p)
         vh = v / (1 - b2p)
-        wd = 0.0 if (self._exclude is not None and self._exclude(p)) else self._wd
+        wd = self._decay_for(p)
         r = mh / (vh.sqrt() + self._eps) + wd * w
         wn = w.norm()
         rn = r.norm()
@@ -211,6 +272,16 @@ class Lamb(_PerParam):
             else torch.ones_like(wn)
         w.sub_(lr * trust * r)
         self._fin(p, master)
+
+    def set_state_dict(self, state_dict):
+        super().set_state_dict(state_dict)
+        for p in self._parameter_list:
+            b1p = self._accumulators.get("beta1_pow_acc", {}).get(id(p))
+            if b1p is not None:
+                v = float(b1p.reshape(-1)[0].item())
+                if 0 < v < 1 and 0 < self._b1 < 1:
+                    self._param_step[id(p)] = int(round(math.log(v) / math.log(self._b1)))
+        self._tables.clear()
 
 
 class NAdam(_PerParam):
