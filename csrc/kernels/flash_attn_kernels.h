@@ -30,12 +30,11 @@
 //     [total, H, D] tensors; LSE / delta are [H, total_q].
 #pragma once
 #include "common.h"
+#include "mfma_tile.h"
 
 using namespace pa;
 
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8_t;
 typedef __attribute__((ext_vector_type(8))) _Float16 f16x8_t;
-typedef __attribute__((ext_vector_type(4))) short s16x4;
 typedef __attribute__((ext_vector_type(16))) float f32x16;
 
 namespace pa_fa {
@@ -110,7 +109,6 @@ __device__ __forceinline__ void lds_barrier() {
 }
 
 // Global loads the compiler does not track: the caller retires them with an explicit counted vmcnt.
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ u32x4 gload16_async(const void* p) {
   u32x4 r;
   asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(r) : "v"(p) : "memory");
@@ -139,28 +137,6 @@ __device__ __forceinline__ uint32_t gload1_async(const void* p) {
 
 __device__ __forceinline__ uint4 lds_b128(const char* smem, int off) {
   return *reinterpret_cast<const uint4*>(smem + off);
-}
-
-__device__ __forceinline__ s16x4 lds_tr(const char* smem, int off) {
-  return __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-      (__attribute__((address_space(3))) s16x4*)(reinterpret_cast<uintptr_t>(smem + off)));
-}
-
-__device__ __forceinline__ void glds16_fa(const void* g, const char* lds) {
-  const uint32_t m0 = __builtin_amdgcn_readfirstlane((uint32_t)reinterpret_cast<uintptr_t>(lds));
-  asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off" ::"v"(g), "s"(m0) : "memory", "m0");
-}
-
-__device__ __forceinline__ void glds4_fa(const void* g, const char* lds) {
-  const uint32_t m0 = __builtin_amdgcn_readfirstlane((uint32_t)reinterpret_cast<uintptr_t>(lds));
-  asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dword %0, off" ::"v"(g), "s"(m0) : "memory", "m0");
-}
-
-__device__ __forceinline__ void raw_barrier() {
-  asm volatile("" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-  asm volatile("" ::: "memory");
-  __builtin_amdgcn_sched_barrier(0);
 }
 
 // 1-D grid of nb * BH workgroups -> (head bh, block rank). Dispatch is round-robin over the 8 XCDs
@@ -390,8 +366,8 @@ __global__ __launch_bounds__(256, MINW) void fa_fwd_kernel(FwdArgs p) {
       const int ch = (img_off<NCH>(row, slot) - row * (NCH * 16)) / 16;  // slot ^ swizzle(row)
       int key = kv0 + row;
       key = key < Sk ? key : Sk - 1;  // rows past the end are masked to -inf below
-      glds16_fa(kbase + (int64_t)key * p.ks[1] + ch * 8, kdst + qq * 1024);
-      glds16_fa(vbase + (int64_t)key * p.vs[1] + ch * 8, vdst + qq * 1024);
+      glds16(kbase + (int64_t)key * p.ks[1] + ch * 8, kdst + qq * 1024);
+      glds16(vbase + (int64_t)key * p.vs[1] + ch * 8, vdst + qq * 1024);
     }
     if (kFm && w == 0) {
       // 64 keys x fm_cols int32 = 16 * fm_cols 16-byte pieces: lanes < 16 * fm_cols
@@ -400,7 +376,7 @@ __global__ __launch_bounds__(256, MINW) void fa_fwd_kernel(FwdArgs p) {
         int key = kv0 + (lane * 4) / p.fm_cols;
         const int part = (lane * 4) % p.fm_cols;
         key = key < Sk ? key : 0;  // (the host pads the key dim to a multiple of 4: a group never crosses it)
-        glds16_fa(fmb + (int64_t)key * p.fm_cols + part, fm_lds + stage * FM_BYTES);
+        glds16(fmb + (int64_t)key * p.fm_cols + part, fm_lds + stage * FM_BYTES);
       }
     }
   };
@@ -413,7 +389,7 @@ __global__ __launch_bounds__(256, MINW) void fa_fwd_kernel(FwdArgs p) {
   if (n_tiles > 0) issue(0, 0);
   for (int t = 0; t < n_tiles; ++t) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this wave's pieces of tile t are in LDS
-    raw_barrier();                                     // ... everyone's, and stage (t+1)&1 is free
+    bar();                                             // ... everyone's, and stage (t+1)&1 is free
     if (kMask) mask_load(t);
     const bool more = t + 1 < n_tiles;
     if (more) issue(t + 1, (t + 1) & 1);
@@ -548,8 +524,8 @@ __global__ __launch_bounds__(256, MINW) void fa_fwd_kernel(FwdArgs p) {
         for (int s = 0; s < 2; ++s) {
           const int R0 = kt * 32 + 16 * s + 4 * hf;
           Frag a;
-          a.h[0] = lds_tr(vs_lds, img_off<NCH>(R0 + qq, cch) + cb);
-          a.h[1] = lds_tr(vs_lds, img_off<NCH>(R0 + 8 + qq, cch) + cb);
+          a.h[0] = lds_tr(vs_lds + (img_off<NCH>(R0 + qq, cch) + cb));
+          a.h[1] = lds_tr(vs_lds + (img_off<NCH>(R0 + 8 + qq, cch) + cb));
           oacc[dt] = mfma32<F16>(a, pf[kt][s], oacc[dt]);
         }
       }
@@ -816,12 +792,12 @@ __global__ __launch_bounds__(NW * 64, 1) void fa_bwd_kernel(BwdArgs p) {
         // A = dS[q=r][key = 16ks + 8hf + j]: transposed read of the dS^T image (rows = keys)
         const int kr0 = 16 * ks + 8 * hf;
         const int ra = kr0 + qq, rb = kr0 + 4 + qq;
-        a.h[0] = lds_tr(dsb, ra * (BM * 2) + (((16 * G1 + 4 * pp) * 2) ^ (((ra >> 2) & 3) << 3)));
-        a.h[1] = lds_tr(dsb, rb * (BM * 2) + (((16 * G1 + 4 * pp) * 2) ^ (((rb >> 2) & 3) << 3)));
+        a.h[0] = lds_tr(dsb + (ra * (BM * 2) + (((16 * G1 + 4 * pp) * 2) ^ (((ra >> 2) & 3) << 3))));
+        a.h[1] = lds_tr(dsb + (rb * (BM * 2) + (((16 * G1 + 4 * pp) * 2) ^ (((rb >> 2) & 3) << 3))));
         // B = K[key = 16ks + 8hf + j][d = dt*32 + r]: transposed read of the K image
         const int cch = (dt * 32 + 16 * G1) / 8 + (pp >> 1);
-        bb.h[0] = lds_tr(k_lds, img_off<NCH>(kr0 + qq, cch) + 8 * (pp & 1));
-        bb.h[1] = lds_tr(k_lds, img_off<NCH>(kr0 + 4 + qq, cch) + 8 * (pp & 1));
+        bb.h[0] = lds_tr(k_lds + (img_off<NCH>(kr0 + qq, cch) + 8 * (pp & 1)));
+        bb.h[1] = lds_tr(k_lds + (img_off<NCH>(kr0 + 4 + qq, cch) + 8 * (pp & 1)));
         qacc = mfma32<F16>(a, bb, qacc);
       }
       // byte offsets into this (b, h)'s dQ rows (row stride H*D floats); out-of-range rows (ragged last
@@ -986,11 +962,11 @@ __global__ __launch_bounds__(NW * 64, 1) void fa_bwd_kernel(BwdArgs p) {
         for (int s = 0; s < 2; ++s) {
           const int R0 = 16 * s + 4 * hf;
           Frag a, cfr;
-          a.h[0] = lds_tr(do_lds, img_off<NCH>(R0 + qq, cch) + cb);
-          a.h[1] = lds_tr(do_lds, img_off<NCH>(R0 + 8 + qq, cch) + cb);
+          a.h[0] = lds_tr(do_lds + (img_off<NCH>(R0 + qq, cch) + cb));
+          a.h[1] = lds_tr(do_lds + (img_off<NCH>(R0 + 8 + qq, cch) + cb));
           dv_acc[dt] = mfma32<F16>(a, pf[s], dv_acc[dt]);
-          cfr.h[0] = lds_tr(q_lds, img_off<NCH>(R0 + qq, cch) + cb);
-          cfr.h[1] = lds_tr(q_lds, img_off<NCH>(R0 + 8 + qq, cch) + cb);
+          cfr.h[0] = lds_tr(q_lds + (img_off<NCH>(R0 + qq, cch) + cb));
+          cfr.h[1] = lds_tr(q_lds + (img_off<NCH>(R0 + 8 + qq, cch) + cb));
           dk_acc[dt] = mfma32<F16>(cfr, sf[s], dk_acc[dt]);
         }
       }
@@ -1053,8 +1029,6 @@ __global__ __launch_bounds__(NW * 64, 1) void fa_bwd_kernel(BwdArgs p) {
 //   dO^T / Q^T come from ds_read_b64_tr_b16 reads of the row images at those query rows.
 //   dQ += dS K over the workgroup's 128 keys through a dS^T LDS image (rows = key, 64-byte rows), wave w owning
 //   d columns 16w..16w+15, fp32 atomics into dq_acc; software-pipelined one block behind like the 4-wave kernel.
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
 template <bool F16>
 __device__ __forceinline__ f32x4 mfma16(const Frag& a, const Frag& b, f32x4 c) {
   if constexpr (F16) return __builtin_amdgcn_mfma_f32_16x16x32_f16(a.f, b.f, c, 0, 0, 0);
@@ -1169,13 +1143,13 @@ __global__ __launch_bounds__(512, 1) void fa_bwd16_kernel(BwdArgs p) {
         p.dout + (varlen ? (int64_t)q_start * p.dos[1] : (int64_t)b * p.dos[0]) + (int64_t)h * p.dos[2];
     const int qx = q0 + pf_row;
     const int qc = qx < Sq ? qx : Sq - 1;
-    glds16_fa(qbase + (int64_t)qc * p.qs[1] + pf_ch * 8, q_st + sl * QT_BYTES + 1024 * w);
-    glds16_fa(dobase + (int64_t)qc * p.dos[1] + pf_ch * 8, do_st + sl * QT_BYTES + 1024 * w);
+    glds16(qbase + (int64_t)qc * p.qs[1] + pf_ch * 8, q_st + sl * QT_BYTES + 1024 * w);
+    glds16(dobase + (int64_t)qc * p.dos[1] + pf_ch * 8, do_st + sl * QT_BYTES + 1024 * w);
     if (w == 0) {
       const int qr = q0 + (lane & 31);
       const int qrc = qr < Sq ? qr : Sq - 1;
       const int64_t lrow = (int64_t)b * p.lse_s[0] + (int64_t)h * p.lse_s[1] + q_start + qrc;
-      glds4_fa(lane < 32 ? (const void*)(p.lse + lrow) : (const void*)(p.delta + lrow), rc_st + sl * 256);
+      glds4(lane < 32 ? (const void*)(p.lse + lrow) : (const void*)(p.delta + lrow), rc_st + sl * 256);
     }
   };
   const float inv_scale = 1.f / p.scale;
@@ -1196,13 +1170,13 @@ __global__ __launch_bounds__(512, 1) void fa_bwd16_kernel(BwdArgs p) {
 #pragma unroll
     for (int ks = 0; ks < 4; ++ks) {
       Frag bb;  // K[key 32ks + 8kg + j][d 16w + r16]
-      bb.h[0] = lds_tr(k_lds, kb0 + 8192 * ks);
-      bb.h[1] = lds_tr(k_lds, kb4 + 8192 * ks);
+      bb.h[0] = lds_tr(k_lds + (kb0 + 8192 * ks));
+      bb.h[1] = lds_tr(k_lds + (kb4 + 8192 * ks));
 #pragma unroll
       for (int qt = 0; qt < 2; ++qt) {
         Frag a;  // dS[q 16qt + r16][key 32ks + 8kg + j] from the dS^T image
-        a.h[0] = lds_tr(dsb, (sb0 ^ (32 * qt)) + 2048 * ks);
-        a.h[1] = lds_tr(dsb, (sb4 ^ (32 * qt)) + 2048 * ks);
+        a.h[0] = lds_tr(dsb + ((sb0 ^ (32 * qt)) + 2048 * ks));
+        a.h[1] = lds_tr(dsb + ((sb4 ^ (32 * qt)) + 2048 * ks));
         qacc[qt] = mfma16<F16>(a, bb, qacc[qt]);
       }
       if (ks & 1) __builtin_amdgcn_sched_barrier(0);
@@ -1229,8 +1203,8 @@ __global__ __launch_bounds__(512, 1) void fa_bwd16_kernel(BwdArgs p) {
   const int64_t nkg = p.ds_rows / 32;
   auto ds_store = [&](const char* dsb, int h, int qb0) {
     Frag a;
-    a.h[0] = lds_tr(dsb, st_o0);
-    a.h[1] = lds_tr(dsb, st_o1);
+    a.h[0] = lds_tr(dsb + st_o0);
+    a.h[1] = lds_tr(dsb + st_o1);
     const u32x4 v = {a.u.x, a.u.y, a.u.z, a.u.w};
     uint16_t* dst = p.ds + (((int64_t)(b * p.H + h) * nkg + kb * 4 + st_ks) * p.ds_ld + qb0 + 16 * st_qt + r16) * 32 +
                     8 * kg;
@@ -1325,11 +1299,11 @@ __global__ __launch_bounds__(512, 1) void fa_bwd16_kernel(BwdArgs p) {
       for (int dt = 0; dt < 8; ++dt) {
         const int tb = ((dt & 1) ? tb1 : tb0) + 512 * (dt >> 1);
         Frag a, c;
-        a.h[0] = lds_tr(do_lds, tb);
-        a.h[1] = lds_tr(do_lds, tb + 4096);
+        a.h[0] = lds_tr(do_lds + tb);
+        a.h[1] = lds_tr(do_lds + (tb + 4096));
         dv_acc[dt] = mfma16<F16>(a, pf, dv_acc[dt]);
-        c.h[0] = lds_tr(q_lds, tb);
-        c.h[1] = lds_tr(q_lds, tb + 4096);
+        c.h[0] = lds_tr(q_lds + tb);
+        c.h[1] = lds_tr(q_lds + (tb + 4096));
         dk_acc[dt] = mfma16<F16>(c, sf, dk_acc[dt]);
         if (dt & 1) __builtin_amdgcn_sched_barrier(0);  // bound the reads in flight (register budget: 2 waves/SIMD)
       }
@@ -1366,22 +1340,22 @@ __global__ __launch_bounds__(512, 1) void fa_bwd16_kernel(BwdArgs p) {
 // dQ of the dS route: dQ[b, q, h, :] = scale * sum_key dS[q][key] K[b, key, hk, :] from the dS tiles written by
 // fa_bwd16_kernel<.., true> (key groups of 32: [ds_ld queries][32 keys] row-major each). One workgroup = 4 waves =
 // 128 queries x 128 d of one (batch, head); key steps of 32 = one key group: the A operand is one contiguous 8 KiB
-// run ([128 q][32 keys], K-major: ds_read_b128 fragments, 16-byte chunks swizzled by ((row >> 3) & 1) << 1), the B
-// operand K [32 keys][128 d] an MN-major image read with ds_read_b64_tr_b16 (the MN-major fragment read of
-// gemm.hip). Both filled by LDS-DMA with the swizzle on the source address. Waves 2 x 2, 64 x 64 outputs each
+// run ([128 q][32 keys], K-major: ds_read_b128 fragments, 16-byte chunks swizzled by k32_swz), the B operand
+// K [32 keys][128 d] an MN-major image swizzled by mn_swz and read with frag<128, false> of mfma_tile.h at
+// s = 0. Both filled by LDS-DMA with the swizzle on the source address. Waves 2 x 2, 64 x 64 outputs each
 // (4 x 4 MFMA 16x16x32 tiles). The dS stream is read once from HBM, so the loop is load-latency bound: a 4-slot LDS
 // ring (64 KiB) keeps three key steps in flight per workgroup and two workgroups share a CU. Causal: key steps up to
 // the block's last visible key; heaviest blocks first.
-__device__ __forceinline__ int dq_swz(int k) { return ((k & 3) | (((k >> 3) & 1) << 2)) << 1; }
-
+// frag<128, false> of mfma_tile.h at s = 0, with the byte offset summed before the image base is added. Kept
+// apart: read through the shared frag, this kernel's compiled code changed.
 __device__ __forceinline__ Frag dq_frag(const char* img, int rbase, int lane) {
   const int g = lane >> 4, i = lane & 15, q = i >> 2, pp = i & 3;
   const int col = rbase + pp * 4;
   const int lc = col >> 3, sub = (col & 7) * 2;
   const int k1 = g * 8 + q, k2 = k1 + 4;
   Frag f;
-  f.h[0] = lds_tr(img, k1 * 256 + ((lc ^ dq_swz(k1)) << 4) + sub);
-  f.h[1] = lds_tr(img, k2 * 256 + ((lc ^ dq_swz(k2)) << 4) + sub);
+  f.h[0] = lds_tr(img + (k1 * 256 + ((lc ^ mn_swz(k1)) << 4) + sub));
+  f.h[1] = lds_tr(img + (k2 * 256 + ((lc ^ mn_swz(k2)) << 4) + sub));
   return f;
 }
 
@@ -1419,19 +1393,19 @@ __global__ __launch_bounds__(256, 2) void fa_bwd_dq_kernel(BwdArgs p) {
   for (int i = 0; i < 2; ++i) {
     const int lin = (i * 4 + w) * 64 + lane;
     const int arow = lin >> 2;
-    aoff[i] = arow * 32 + (((lin & 3) ^ (((arow >> 3) & 1) << 1)) * 8);
+    aoff[i] = arow * 32 + (((lin & 3) ^ k32_swz(arow)) * 8);
     srow[i] = lin >> 4;
-    scol[i] = ((lin & 15) ^ dq_swz(srow[i])) * 8;
+    scol[i] = ((lin & 15) ^ mn_swz(srow[i])) * 8;
   }
   auto issue = [&](int t) {
     char* a_img = smem + (t % NS) * 2 * TB;
     char* b_img = a_img + TB;
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
-      glds16_fa(ds + t * ds_grp + aoff[i], a_img + (i * 4 + w) * 1024);
+      glds16(ds + t * ds_grp + aoff[i], a_img + (i * 4 + w) * 1024);
       const int key = t * 32 + srow[i];
       const int kc = key < p.Sk ? key : p.Sk - 1;
-      glds16_fa(kb + (int64_t)kc * p.ks[1] + scol[i], b_img + (i * 4 + w) * 1024);
+      glds16(kb + (int64_t)kc * p.ks[1] + scol[i], b_img + (i * 4 + w) * 1024);
     }
   };
 
@@ -1452,7 +1426,7 @@ __global__ __launch_bounds__(256, 2) void fa_bwd_dq_kernel(BwdArgs p) {
 #pragma unroll
     for (int i = 0; i < 4; ++i) {  // A[q = row][keys 8c..8c+7], c = lane >> 4
       const int row = wm * 64 + i * 16 + (lane & 15);
-      af[i].u = lds_b128(a_img, row * 64 + (((lane >> 4) ^ (((row >> 3) & 1) << 1)) << 4));
+      af[i].u = lds_b128(a_img, row * 64 + (((lane >> 4) ^ k32_swz(row)) << 4));
     }
 #pragma unroll
     for (int j = 0; j < 4; ++j) bf[j] = dq_frag(b_img, wn * 64 + j * 16, lane);

@@ -16,14 +16,15 @@
 //   * 256 x BN x 64 tiles, 8 waves (512 threads) as 2 (M) x 4 (N); per wave 128 x BN/4;
 //     v_mfma_f32_16x16x32_bf16, operands swapped (D = B^T-frag x A-frag) so each lane ends with
 //     4 consecutive output columns of one row -> 8/16-byte epilogue stores.
-//   * global -> LDS with global_load_lds_dwordx4 (no VGPR staging), two LDS stages (128 KiB for
+//   * the LDS tile primitives (glds16 LDS-DMA, lds_tr, bar, vm_wait, the swizzles, stage<R, KMAJ, NW>,
+//     frag<R, KMAJ>, xcd_remap, tile_coords) are the shared ones of mfma_tile.h; this file keeps what is its
+//     own: the K-loops and schedules, Loader32 / frag32, the conv gathers and the epilogues.
+//   * global -> LDS by LDS-DMA (glds16, no VGPR staging), two LDS stages (128 KiB for
 //     256x256): tile t+1 is in flight while tile t is consumed.
-//   * K-major images: [rows][64 k] with 128-B rows, 16-B chunk XOR-swizzle chunk ^ ((row>>1)&7):
+//   * K-major images: [rows][64 k] with 128-B rows, 16-B chunk XOR-swizzle chunk ^ k_swz(row):
 //     the ds_read_b128 of 16 rows x one chunk hits 16 distinct bank slots.
 //   * MN-major images: [64 k][R] rows, read with ds_read_b64_tr_b16 (hardware transpose) and
-//     swizzled chunk ^ 2*((k&3) | ((k>>3)&1)<<2) so each 32-lane half reads 8 distinct 32-B slots.
-//   * glds writes LDS lane-linearly, so the swizzle is applied to the per-lane GLOBAL source address
-//     and undone on the LDS read (both sides or neither).
+//     swizzled chunk ^ mn_swz_r<R>(k) so each 32-lane half reads 8 distinct 32-B slots.
 //   * XCD-aware bijective block remap + grouped tile order so the blocks of one XCD share A / B
 //     panels in their private L2.
 //   * epilogue: + bias[N], tanh-GELU (optionally storing the pre-activation for the backward),
@@ -31,22 +32,13 @@
 #include "common.h"
 #include "gemm_plan.h"
 #include "launch.h"
+#include "mfma_tile.h"
 
 #include <type_traits>
 
 using namespace pa;
 
 namespace {
-
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8_t;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef __attribute__((ext_vector_type(4))) short s16x4;
-
-union Frag8 {
-  bf16x8_t v;
-  uint4 u;
-  s16x4 h[2];
-};
 
 constexpr int kBM = 256;
 constexpr int kBK = 64;
@@ -177,58 +169,6 @@ __device__ __forceinline__ void stats_add2(uint32_t packed, float* s1, float* s2
   s1[e + 1] += b; s2[e + 1] += b * b;
 }
 
-// global_load_lds_dwordx4 issued from inline asm: hipcc treats a builtin LDS-DMA as a pending write to
-// every LDS object and puts s_waitcnt vmcnt(0) in front of the next ds_read, which would drain the
-// prefetch pipeline each phase. The kernels retire the DMA themselves with counted vmcnt + barrier.
-// M0 holds the wave-uniform LDS destination (lane i writes base + 16 i).
-__device__ __forceinline__ void glds16(const void* g, char* lds_wave_base) {
-  const uint32_t m0 = __builtin_amdgcn_readfirstlane((uint32_t)reinterpret_cast<uintptr_t>(lds_wave_base));
-  asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off" ::"v"(g), "s"(m0) : "memory", "m0");
-}
-
-__device__ __forceinline__ s16x4 lds_tr(const char* p) {
-  return __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-      (__attribute__((address_space(3))) s16x4*)(reinterpret_cast<uintptr_t>(p)));
-}
-
-// swizzle of an MN-major image row (even chunk XOR so 32-B pairs stay together)
-__device__ __forceinline__ int mn_swz(int k) { return ((k & 3) | (((k >> 3) & 1) << 2)) << 1; }
-// the swizzle restricted to a k-row of R columns (R / 8 chunks): a no-op for R >= 128; for R = 64 it keeps
-// the chunk inside its row (slot <-> global chunk stays a bijection)
-template <int R>
-__device__ __forceinline__ int mn_swz_r(int k) { return mn_swz(k) & (R / 8 - 1); }
-
-// ---- staging of one operand tile (R rows of the output dimension x 64 k) into LDS
-// K-major: image [R][64] (128-B rows).  MN-major: image [64][R] (2R-byte rows).
-template <int R, bool KMAJ, int NW = 8>
-__device__ __forceinline__ void stage(const uint16_t* __restrict__ g, int64_t ld, int r0, int rmax, int k0,
-                                      char* img, int wave, int lane) {
-  constexpr int NQ = R / (8 * NW);  // glds instructions per thread (R*64*2 bytes / (NW * 64 * 16))
-  if constexpr (KMAJ) {
-#pragma unroll
-    for (int i = 0; i < NQ; ++i) {
-      const int q = i * NW + wave;              // wave-instruction id: 8 rows x 128 B
-      const int row = q * 8 + (lane >> 3);
-      const int lc = (lane & 7) ^ ((row >> 1) & 7);
-      int gr = r0 + row;
-      gr = gr < rmax ? gr : rmax - 1;
-      glds16(g + (int64_t)gr * ld + k0 + lc * 8, img + q * 1024);
-    }
-  } else {
-    constexpr int CPR = R / 8;  // 16-B chunks per k-row
-#pragma unroll
-    for (int i = 0; i < NQ; ++i) {
-      const int q = i * NW + wave;
-      const int lin = q * 64 + lane;
-      const int row = lin / CPR;                // k
-      const int lc = (lin % CPR) ^ mn_swz_r<R>(row);
-      int gc = r0 + lc * 8;
-      gc = gc < rmax ? gc : rmax - 8;
-      glds16(g + (int64_t)(k0 + row) * ld + gc, img + q * 1024);
-    }
-  }
-}
-
 // Weight gradient of a KxK NHWC convolution as a GEMM: dW^T[m = (kh*KW + kw)*C + c][n = co] =
 //   sum_p x[n_img, ho*s - pad + kh*dil, wo*s - pad + kw*dil, c] * dy[p][co],  p = (n_img, ho, wo).
 // A (M x K, MN-major: 8 consecutive m are 8 channels of one tap) is gathered per (pixel, tap) here; the
@@ -289,30 +229,6 @@ __device__ __forceinline__ void stage_convw(const GemmArgs& p, const ConvWState<
     const uint16_t* src = ok ? p.a + (((int64_t)st.n[i] * p.cH + hi) * p.cW + wi) * p.cC + st.c[i] : p.zero;
     glds16(src, img + q * 1024);
   }
-}
-
-// ---- fragment read: 16 rows (output dim) x 8 k for k-substep s (32 k) -> mfma operand
-template <int R, bool KMAJ>
-__device__ __forceinline__ bf16x8_t frag(const char* img, int rbase, int s, int lane) {
-  Frag8 f;
-  if constexpr (KMAJ) {
-    const int row = rbase + (lane & 15);
-    const int c = s * 4 + (lane >> 4);
-    f.u = *reinterpret_cast<const uint4*>(img + row * 128 + ((c ^ ((row >> 1) & 7)) << 4));
-  } else {
-    const int g = lane >> 4, i = lane & 15, q = i >> 2, pp = i & 3;
-    const int col = rbase + pp * 4;           // first of 4 columns supplied by this lane
-    const int lc = col >> 3, sub = (col & 7) * 2;
-    const int k1 = s * 32 + g * 8 + q, k2 = k1 + 4;
-    f.h[0] = lds_tr(img + k1 * (R * 2) + ((lc ^ mn_swz_r<R>(k1)) << 4) + sub);
-    f.h[1] = lds_tr(img + k2 * (R * 2) + ((lc ^ mn_swz_r<R>(k2)) << 4) + sub);
-  }
-  return f.v;
-}
-
-__device__ __forceinline__ int xcd_remap(int bid, int nwg) {
-  const int xcd = bid & 7, q = nwg >> 3, r = nwg & 7;
-  return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
 }
 
 // segment of a K-tile / column index v (wave-uniform: constant-index selects, no dynamic kernel-argument indexing)
@@ -480,43 +396,9 @@ __global__ __launch_bounds__(NW * 64, 1) void gemm_bf16_kernel(GemmArgs p0) {
 // happens at least one barrier after the wait that retires it in both wave groups (RAW).
 // Wave (wm, wn) owns rows {wm*64.., 128+wm*64..} x cols {wn*32.., 128+wn*32..}: the four phases
 // compute its quadrants (top,L) (top,R) (bottom,L) (bottom,R).
-__device__ __forceinline__ void bar() {
-  asm volatile("" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-  asm volatile("" ::: "memory");
-  __builtin_amdgcn_sched_barrier(0);
-}
-
-// s_waitcnt vmcnt(n) for a wave-uniform runtime n (the immediate must be a literal)
-__device__ __forceinline__ void vm_wait(int n) {
-  switch (n) {
-    case 0: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
-    case 2: asm volatile("s_waitcnt vmcnt(2)" ::: "memory"); break;
-    case 4: asm volatile("s_waitcnt vmcnt(4)" ::: "memory"); break;
-    case 6: asm volatile("s_waitcnt vmcnt(6)" ::: "memory"); break;
-    case 8: asm volatile("s_waitcnt vmcnt(8)" ::: "memory"); break;
-    case 10: asm volatile("s_waitcnt vmcnt(10)" ::: "memory"); break;
-    default: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
-  }
-}
-
-// grouped tile order (8 m-tiles per group, so neighbouring workgroups share B panels)
-__device__ __forceinline__ void tile_coords(int pid, int tiles_m, int tiles_n, int* tm, int* tn) {
-  constexpr int GM = 8;
-  const int per_group = GM * tiles_n;
-  const int first_m = (pid / per_group) * GM;
-  const int gsz = min(tiles_m - first_m, GM);
-  *tm = first_m + (pid % per_group) % gsz;
-  *tn = (pid % per_group) / gsz;
-}
-
 constexpr int kEpiRowStride = 260;      // fp32 per row of the epilogue image (256 + 4 padding)
 constexpr int kEpiRowStrideBf16 = 264;  // bf16 per row of the one-pass bf16 epilogue image (528-byte rows)
 
-template <int V>
-struct IntC {
-  static constexpr int value = V;
-};
 using H0_ = IntC<0>;
 using H1_ = IntC<1>;
 using H2_ = IntC<2>;
@@ -956,12 +838,9 @@ __global__ __launch_bounds__(kThreads, 1) void gemm256_kernel(GemmArgs p0) {
 //   * K-tiles of 32 in a 4-slot LDS ring (4 x 32 KiB): tile t+1 is read into the second fragment register set
 //     while the 64 MFMAs of tile t run; tiles t+2, t+3 (+ t+4 issued after the barrier) stay in flight, so a
 //     glds has three K-tiles (~3k cycles) to land. One barrier per K-tile.
-//   * K-major images [256][32] (64-B rows) with the chunk swizzle c ^ 2*((row >> 3) & 1): the 16 rows x 4 chunks
+//   * K-major images [256][32] (64-B rows) with the chunk swizzle c ^ k32_swz(row): the 16 rows x 4 chunks
 //     of one fragment ds_read_b128 hit 16 distinct 16-B bank slots in each lane group. MN-major images [32][256]
 //     (512-B rows) use the mn_swz swizzle and ds_read_b64_tr_b16 like the kernels above.
-__device__ __forceinline__ int k32_swz(int row) { return ((row >> 3) & 1) << 1; }
-
-typedef int i32x4 __attribute__((ext_vector_type(4)));
 
 // LDS-DMA staging of one operand's 256 x 32 tile through buffer_load_dwordx4 ... lds: the buffer descriptor
 // holds the tile's base address (advanced by scalar adds per K-tile), each lane's byte offset inside the tile
@@ -1203,6 +1082,12 @@ __global__ __launch_bounds__(256, 1) void gemm4w_kernel(GemmArgs p) {
 // ds_read_b64_tr_b16 half-wave land on 8 distinct 32-B slots.
 constexpr int kBN3 = 160;
 
+// MN-major swizzle of this kernel's images, stage_r and frag_r together: R = 160 takes the 32-B XOR alone
+template <int R>
+__device__ __forceinline__ int mn_swz3(int k) { return R == 160 ? k32_swz(k) : mn_swz(k); }
+
+// stage / frag of mfma_tile.h for R = 160, which 8 waves do not divide. Kept apart from the shared pair: the fold
+// would change the code compiled for the two-stage kernel's 160-column instantiations (see launch<BN, ..> below).
 template <int R, bool KMAJ>
 __device__ __forceinline__ void stage_r(const uint16_t* __restrict__ g, int64_t ld, int r0, int rmax, int k0,
                                         char* img, int wave, int lane) {
@@ -1214,7 +1099,7 @@ __device__ __forceinline__ void stage_r(const uint16_t* __restrict__ g, int64_t 
     if (q >= NI) q -= 8 * PER - NI;       // same bytes to the same LDS place: a benign duplicate
     if constexpr (KMAJ) {
       const int row = q * 8 + (lane >> 3);
-      const int lc = (lane & 7) ^ ((row >> 1) & 7);
+      const int lc = (lane & 7) ^ k_swz(row);
       int gr = r0 + row;
       gr = gr < rmax ? gr : rmax - 1;
       glds16(g + (int64_t)gr * ld + k0 + lc * 8, img + q * 1024);
@@ -1222,7 +1107,7 @@ __device__ __forceinline__ void stage_r(const uint16_t* __restrict__ g, int64_t 
       constexpr int CPR = R / 8;
       const int lin = q * 64 + lane;
       const int row = lin / CPR;
-      const int sw = (R == 160) ? (((row >> 3) & 1) << 1) : mn_swz(row);
+      const int sw = mn_swz3<R>(row);
       const int lc = (lin % CPR) ^ sw;
       int gc = r0 + lc * 8;
       gc = gc < rmax ? gc : rmax - 8;
@@ -1241,8 +1126,8 @@ __device__ __forceinline__ bf16x8_t frag_r(const char* img, int rbase, int s, in
     const int col = rbase + pp * 4;
     const int lc = col >> 3, sub = (col & 7) * 2;
     const int k1 = s * 32 + g * 8 + q, k2 = k1 + 4;
-    f.h[0] = lds_tr(img + k1 * (R * 2) + ((lc ^ (((k1 >> 3) & 1) << 1)) << 4) + sub);
-    f.h[1] = lds_tr(img + k2 * (R * 2) + ((lc ^ (((k2 >> 3) & 1) << 1)) << 4) + sub);
+    f.h[0] = lds_tr(img + k1 * (R * 2) + ((lc ^ mn_swz3<R>(k1)) << 4) + sub);
+    f.h[1] = lds_tr(img + k2 * (R * 2) + ((lc ^ mn_swz3<R>(k2)) << 4) + sub);
     return f.v;
   }
 }
@@ -1285,7 +1170,7 @@ __device__ __forceinline__ void stage_conv(const GemmArgs& p, const ConvRows& cr
   for (int i = 0; i < 4; ++i) {
     const int q = i * 8 + wave;
     const int row = q * 8 + (lane >> 3);
-    const int lc = (lane & 7) ^ ((row >> 1) & 7);
+    const int lc = (lane & 7) ^ k_swz(row);
     const int di = cr.db[i] + kd * p.cDil, hi = cr.hb[i] + kh * p.cDil, wi = cr.wb[i] + kw * p.cDil;
     const bool ok = cr.pix[i] >= 0 && di >= 0 && di < p.cD && hi >= 0 && hi < p.cH && wi >= 0 && wi < p.cW;
     const uint16_t* src =

@@ -11,21 +11,21 @@
 //
 // Structure: the bf16 generic kernel's (gemm.hip gemm_bf16_kernel) at the same bytes: 256 x 256 tiles,
 // 128 k (= 128 bytes) per stage, 8 waves as 2 (M) x 4 (N) with a 128 x 64 wave tile, two LDS stages of
-// 64 KiB fed by global_load_lds_dwordx4, 16-B chunk XOR swizzle on 128-B rows. Fragments: lane l holds row
-// (l & 15) and the 32 k-bytes [32 (l >> 4), 32 (l >> 4) + 32) for A and for B alike, so any k permutation
+// 64 KiB fed by LDS-DMA, 16-B chunk XOR swizzle on 128-B rows (stage<R, true> of mfma_tile.h on bytes: the
+// bf16 K-major image byte for byte). Fragments: lane l holds row (l & 15) and the 32 k-bytes [32 (l >> 4), 32 (l >> 4) + 32) for A and for B alike, so any k permutation
 // the instruction applies inside its 128-k block is the same on both operands (and with unit block scales
 // no scale placement matters). Operands are swapped (D = B-frag x A-frag) so a lane ends with 4
 // consecutive columns of one output row.
 #include "common.h"
 #include "gemm_plan.h"
 #include "launch.h"
+#include "mfma_tile.h"
 
 using namespace pa;
 
 namespace {
 
 typedef __attribute__((ext_vector_type(8))) int i32x8;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
 
 constexpr int kTile = 256;
 constexpr int kKB = 128;  // bytes (= fp8 elements) of k per stage
@@ -48,28 +48,10 @@ struct Fp8Args {
   float* tail_ws;
 };
 
-__device__ __forceinline__ void glds16(const void* g, char* lds_wave_base) {
-  const uint32_t m0 = __builtin_amdgcn_readfirstlane((uint32_t)reinterpret_cast<uintptr_t>(lds_wave_base));
-  asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off" ::"v"(g), "s"(m0) : "memory", "m0");
-}
-
-// one operand tile: 256 rows x 128 k-bytes -> LDS image [256][128 B], chunk c of row r at c ^ ((r >> 1) & 7)
-__device__ __forceinline__ void stage_op(const uint8_t* __restrict__ g, int64_t ld, int r0, int rmax, int k0,
-                                         char* img, int wave, int lane) {
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const int q = i * 8 + wave;  // 8 rows x 128 B per wave instruction
-    const int row = q * 8 + (lane >> 3);
-    const int lc = (lane & 7) ^ ((row >> 1) & 7);
-    int gr = r0 + row;
-    gr = gr < rmax ? gr : rmax - 1;
-    glds16(g + (int64_t)gr * ld + k0 + lc * 16, img + q * 1024);
-  }
-}
-
+// fragment of a stage<R, true> image [R][128 B]: the lane's two chunks of its row, k_swz undone
 __device__ __forceinline__ i32x8 frag(const char* img, int rbase, int lane) {
   const int row = rbase + (lane & 15);
-  const int c0 = 2 * (lane >> 4), sw = (row >> 1) & 7;
+  const int c0 = 2 * (lane >> 4), sw = k_swz(row);
   // chunks c0, c0 + 1 (c0 even) sit at (c0 ^ sw) and (c0 ^ sw) ^ 1: the second address is the first XOR 16
   const int off = row * 128 + ((c0 ^ sw) << 4);
   const uint4 lo = *reinterpret_cast<const uint4*>(img + off);
@@ -78,11 +60,6 @@ __device__ __forceinline__ i32x8 frag(const char* img, int rbase, int lane) {
   f[0] = (int)lo.x; f[1] = (int)lo.y; f[2] = (int)lo.z; f[3] = (int)lo.w;
   f[4] = (int)hi.x; f[5] = (int)hi.y; f[6] = (int)hi.z; f[7] = (int)hi.w;
   return f;
-}
-
-__device__ __forceinline__ int xcd_remap(int bid, int nwg) {
-  const int xcd = bid & 7, q = nwg >> 3, r = nwg & 7;
-  return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
 }
 
 __device__ __forceinline__ float act_f(float v, int act) {
@@ -116,8 +93,8 @@ __global__ __launch_bounds__(512, 1) void gemm_fp8_kernel(Fp8Args p) {
 
   auto stage_tile = [&](int t, int buf) {
     char* base = smem + buf * kStage;
-    stage_op(p.a, p.lda, m0, p.M, t * kKB, base, wave, lane);
-    stage_op(p.b, p.ldb, n0, p.N, t * kKB, base + kOpBytes, wave, lane);
+    stage<kTile, true>(p.a, p.lda, m0, p.M, t * kKB, base, wave, lane);
+    stage<kTile, true>(p.b, p.ldb, n0, p.N, t * kKB, base + kOpBytes, wave, lane);
   };
 
   const int nk = p.K / kKB;
@@ -182,39 +159,7 @@ __global__ __launch_bounds__(512, 1) void gemm_fp8_kernel(Fp8Args p) {
 // MFMAs' cycles at twice the FLOPs). Fragments: lane l holds row (l & 15) and k-bytes [32 (l >> 4), +32) of the
 // 128-byte row (chunks 2g, 2g + 1). Wave (wm, wn) owns rows {wm*64.., 128+wm*64..} x cols {wn*32.., 128+wn*32..}.
 // Epilogue: alpha, bias, activation in registers, the 16-bit tile staged through LDS, 16-byte row stores
-// (N % 8 == 0).
-__device__ __forceinline__ void bar() {
-  asm volatile("" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-  asm volatile("" ::: "memory");
-  __builtin_amdgcn_sched_barrier(0);
-}
-
-__device__ __forceinline__ void vm_wait(int n) {
-  switch (n) {
-    case 0: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
-    case 2: asm volatile("s_waitcnt vmcnt(2)" ::: "memory"); break;
-    case 4: asm volatile("s_waitcnt vmcnt(4)" ::: "memory"); break;
-    case 6: asm volatile("s_waitcnt vmcnt(6)" ::: "memory"); break;
-    case 8: asm volatile("s_waitcnt vmcnt(8)" ::: "memory"); break;
-    case 10: asm volatile("s_waitcnt vmcnt(10)" ::: "memory"); break;
-    default: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
-  }
-}
-
-// one half-tile: 128 rows x 128 k-bytes -> LDS [128][128 B], chunk c of row r at c ^ ((r >> 1) & 7); 2 glds / lane
-__device__ __forceinline__ void stage_half8(const uint8_t* __restrict__ g, int64_t ld, int r0, int rmax, int k0,
-                                            char* img, int wave, int lane) {
-#pragma unroll
-  for (int i = 0; i < 2; ++i) {
-    const int q = i * 8 + wave;
-    const int row = q * 8 + (lane >> 3);
-    const int lc = (lane & 7) ^ ((row >> 1) & 7);
-    int gr = r0 + row;
-    gr = gr < rmax ? gr : rmax - 1;
-    glds16(g + (int64_t)gr * ld + k0 + lc * 16, img + q * 1024);
-  }
-}
+// (N % 8 == 0). bar, vm_wait, xcd_remap, tile_coords and IntC are the bf16 kernel's own, from mfma_tile.h.
 
 // C += B-frag x A-frag on the unscaled v_mfma_f32_16x16x128_f8f6f4 (formats in cbsz / blgp); PA_FP8_SCALED_MFMA
 // selects the block-scaled form with unit E8M0 scales instead (the builtin: an extra scale operand pair).
@@ -236,28 +181,13 @@ __device__ __forceinline__ f32x4 mfma8(const i32x8& b, const i32x8& a, f32x4 c) 
 #endif
 }
 
-template <int V>
-struct IntC {
-  static constexpr int value = V;
-};
-
-// grouped tile order (8 m-tiles per group), as gemm.hip tile_coords
-__device__ __forceinline__ void tile_coords8(int pid, int tiles_m, int tiles_n, int* tm, int* tn) {
-  constexpr int GM = 8;
-  const int per_group = GM * tiles_n;
-  const int first_m = (pid / per_group) * GM;
-  const int gsz = min(tiles_m - first_m, GM);
-  *tm = first_m + (pid % per_group) % gsz;
-  *tn = (pid % per_group) / gsz;
-}
-
 // balanced-tail reduction: tail tile b = tile full_tiles + b; a thread sums the slices' partials of 4 columns and
 // applies the epilogue
 template <bool OUT_F16>
 __global__ __launch_bounds__(256) void gemm_fp8_tail_reduce_k(Fp8Args p) {
   const int b = blockIdx.x;
   int tm, tn;
-  tile_coords8(p.full_tiles + b, p.tiles_m, p.tiles_n, &tm, &tn);
+  tile_coords(p.full_tiles + b, p.tiles_m, p.tiles_n, &tm, &tn);
   const int e = (blockIdx.y * 256 + threadIdx.x) * 4;
   const int r = e >> 8, c = e & 255;
   const int m = tm * 256 + r, n = tn * 256 + c;
@@ -312,14 +242,14 @@ __global__ __launch_bounds__(kPPThreads, 1) void gemm_fp8_pp_kernel(Fp8Args p) {
     pid = xcd_remap(bid, p.tail_split > 0 ? p.full_tiles : p.tiles_m * p.tiles_n);
   }
   int tm, tn;
-  tile_coords8(pid, p.tiles_m, p.tiles_n, &tm, &tn);
+  tile_coords(pid, p.tiles_m, p.tiles_n, &tm, &tn);
   const int m0 = tm * kTile, n0 = tn * kTile;
   const int nk = p.K / kKB;
 
   auto stage_h = [&](int t, int h, char* dst) {
     const int k0 = t * kKB;
-    if (h == 0 || h == 2) stage_half8(p.a, p.lda, m0 + (h == 2 ? 128 : 0), p.M, k0, dst, wave, lane);
-    else stage_half8(p.b, p.ldb, n0 + (h == 3 ? 128 : 0), p.N, k0, dst, wave, lane);
+    if (h == 0 || h == 2) stage<128, true>(p.a, p.lda, m0 + (h == 2 ? 128 : 0), p.M, k0, dst, wave, lane);
+    else stage<128, true>(p.b, p.ldb, n0 + (h == 3 ? 128 : 0), p.N, k0, dst, wave, lane);
   };
   auto issue = [&](int j) {
     const int t = j >> 2, h = j & 3;

@@ -12,21 +12,12 @@
 //     them as one 16-byte store (no LDS round trip for the epilogue).
 // Reference role: the cuDNN 1x1-convolution kernels behind paddle/phi/kernels/gpu/conv_kernel.cu.
 #include "common.h"
+#include "mfma_tile.h"
 
 #include <cstdlib>
 
 namespace {
 using namespace pa;
-
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8_t;
-
-union Frag8 {
-  bf16x8_t v;
-  uint4 u;
-  u32x4 w;
-};
 
 constexpr int kSkEpiBias = 1;
 constexpr int kSkEpiAccum = 2;
@@ -423,15 +414,10 @@ int launch_skconv(const SkConvArgs& a, hipStream_t st) {
 
 // ---- 3x3, stride 1, pad 1, C = Cout = 64 on a per-wave LDS halo tile. A wave owns a segment of 16 output pixels of
 // one image row; its input window (3 rows x 18 pixels x 64 channels = 6.75 KB) arrives in 7 LDS-DMA instructions
-// (global_load_lds_dwordx4, padding pixels fetched from a zero page), so the 9 taps' A fragments are LDS reads
+// (glds16, padding pixels fetched from a zero page), so the 9 taps' A fragments are LDS reads
 // instead of 18 per-tap HBM / L2 gathers. The 16-byte channel chunks of a pixel are XOR-swizzled by the pixel
 // index (conflict-free 16-lane row reads). All 18 A fragments are read into registers before the MFMAs, and the
 // next segment's DMA is issued right then, so the window load overlaps this segment's 72 MFMAs.
-__device__ __forceinline__ void sk_glds16(const void* g, char* lds_wave_base) {
-  const uint32_t m0 = __builtin_amdgcn_readfirstlane((uint32_t)reinterpret_cast<uintptr_t>(lds_wave_base));
-  asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off" ::"v"(g), "s"(m0) : "memory", "m0");
-}
-
 struct SkHaloArgs {
   const uint16_t* x;
   const uint16_t* w;   // [64][3][3][64]
@@ -487,7 +473,7 @@ __global__ __launch_bounds__(NW * 64) void skinny_conv_halo_k(SkHaloArgs p) {
       const int ch = chs ^ (px & 7);
       const bool ok = q < SLOTS && (unsigned)hi < (unsigned)p.H && (unsigned)wi < (unsigned)p.W;
       const uint16_t* src = ok ? p.x + (((int64_t)n * p.H + hi) * p.W + wi) * C + 8 * ch : p.zero + 8 * (q & 7);
-      sk_glds16(src, tile + 1024 * i);
+      glds16(src, tile + 1024 * i);
     }
   };
   const int brow = 8 * (r >> 2) + (r & 3);
@@ -598,11 +584,6 @@ int launch_halo(const SkHaloArgs& a, hipStream_t st) {
 // operands are pixel-contiguous columns of those row-major tiles, read with ds_read_b64_tr_b16 (the hardware
 // transpose). Each wave accumulates its tap's 64 x 64 block (16 tiles of 16x16) over the pieces and writes an fp32
 // slab per workgroup; the slabs are summed afterwards (split over pixels).
-typedef short s16x4_t __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ s16x4_t sk_lds_tr(const char* p) {
-  return __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-      (__attribute__((address_space(3))) s16x4_t*)(reinterpret_cast<uintptr_t>(p)));
-}
 
 // 16-byte chunk swizzle of a 128-byte pixel row of the weight-gradient tiles: pixels 4 apart (the rows of one
 // transposed read) and 8 apart (the two 16-lane groups of a half-wave) land on different banks
@@ -648,7 +629,7 @@ __global__ __launch_bounds__(576) void skinny_wgrad3_k(SkWgArgs p) {
         if ((unsigned)hi < (unsigned)p.H && (unsigned)wi < (unsigned)p.W)
           src = p.x + (((int64_t)n * p.H + hi) * p.W + wi) * C + 8 * ch;
       }
-      sk_glds16(src, lds + st * STAGE + 1024 * (9 * i + wave));
+      glds16(src, lds + st * STAGE + 1024 * (9 * i + wave));
     }
   };
   f32x4 acc[4][4];
@@ -678,8 +659,8 @@ __global__ __launch_bounds__(576) void skinny_wgrad3_k(SkWgArgs p) {
 #pragma unroll
       for (int h = 0; h < 2; ++h) {
         const int pa = 8 * g + 4 * h + q, pb = pa + kw;  // dY tile pixel, window pixel of this lane's row
-        const s16x4_t va = sk_lds_tr(dyt + pa * 128 + (((2 * t + (pp >> 1)) ^ wg_swz(pa)) << 4) + 8 * (pp & 1));
-        const s16x4_t vb = sk_lds_tr(win + (kh * 34 + pb) * 128 + (((2 * t + (pp >> 1)) ^ wg_swz(pb)) << 4) +
+        const s16x4 va = lds_tr(dyt + pa * 128 + (((2 * t + (pp >> 1)) ^ wg_swz(pa)) << 4) + 8 * (pp & 1));
+        const s16x4 vb = lds_tr(win + (kh * 34 + pb) * 128 + (((2 * t + (pp >> 1)) ^ wg_swz(pb)) << 4) +
                                      8 * (pp & 1));
         af[t].u = h == 0 ? make_uint4(__builtin_bit_cast(uint2, va).x, __builtin_bit_cast(uint2, va).y, af[t].u.z,
                                       af[t].u.w)

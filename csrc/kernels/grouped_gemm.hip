@@ -17,24 +17,16 @@
 // Tiles: 128 x 128 x 64 with 4 waves (2 x 2, 64 x 64 per wave) for small experts, 256 x 256 x 64 with 8
 // waves (2 x 4, 128 x 64 per wave) when the experts hold >= 1024 rows on average; v_mfma_f32_16x16x32_bf16
 // with operands swapped so a lane ends with 4 consecutive output columns of one row. Both operands go
-// global -> LDS with global_load_lds_dwordx4 into two stages, K-major images XOR-swizzled per 16-B chunk,
-// MN-major images read with ds_read_b64_tr_b16.
+// global -> LDS by LDS-DMA into two stages, K-major images XOR-swizzled per 16-B chunk, MN-major images read
+// with ds_read_b64_tr_b16: the shared primitives of mfma_tile.h (glds16, stage<R, true, NW>, frag<R, KMAJ>,
+// mn_swz_r). Only stage_mn is this file's own: it reads the zero page past the expert's last token.
 #include "common.h"
 #include "launch.h"
+#include "mfma_tile.h"
 
 using namespace pa;
 
 namespace {
-
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8_t;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef __attribute__((ext_vector_type(4))) short s16x4;
-
-union Frag8 {
-  bf16x8_t v;
-  uint4 u;
-  s16x4 h[2];
-};
 
 constexpr int kK = 64;  // k per stage
 enum : int { kGBias = 1, kGAccum = 2, kGOutF32 = 4 };
@@ -53,35 +45,8 @@ struct GGArgs {
   int flags;
 };
 
-__device__ __forceinline__ void glds16(const void* g, char* lds_wave_base) {
-  const uint32_t m0 = __builtin_amdgcn_readfirstlane((uint32_t)reinterpret_cast<uintptr_t>(lds_wave_base));
-  asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off" ::"v"(g), "s"(m0) : "memory", "m0");
-}
-
-__device__ __forceinline__ s16x4 lds_tr(const char* p) {
-  return __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-      (__attribute__((address_space(3))) s16x4*)(reinterpret_cast<uintptr_t>(p)));
-}
-
-// MN-major image swizzle (chunk XOR within a 256-B k-row of 16 chunks)
-__device__ __forceinline__ int mn_swz(int k) { return ((k & 3) | (((k >> 3) & 1) << 2)) << 1; }
-
-// K-major tile: R rows from r0 (clamped to rmax - 1; clamped rows are never stored) x 64 k from k0
-template <int R, int NW>
-__device__ __forceinline__ void stage_k(const uint16_t* __restrict__ g, int64_t ld, int r0, int rmax, int k0,
-                                        char* img, int wave, int lane) {
-#pragma unroll
-  for (int i = 0; i < R / (8 * NW); ++i) {
-    const int q = i * NW + wave;
-    const int row = q * 8 + (lane >> 3);
-    const int lc = (lane & 7) ^ ((row >> 1) & 7);
-    int gr = r0 + row;
-    gr = gr < rmax ? gr : rmax - 1;
-    glds16(g + (int64_t)gr * ld + k0 + lc * 8, img + q * 1024);
-  }
-}
-
-// MN-major tile: 64 k-rows from k0 (rows >= kend read the zero page) x R columns from c0 (clamped)
+// MN-major tile: 64 k-rows from k0 (rows >= kend read the zero page, which stage<R, false> does not do) x R
+// columns from c0 (clamped); the image is the one frag<R, false> reads
 template <int R, int NW>
 __device__ __forceinline__ void stage_mn(const uint16_t* __restrict__ g, int64_t ld, int c0, int cmax, int k0,
                                          int kend, const uint16_t* zero, char* img, int wave, int lane) {
@@ -91,31 +56,13 @@ __device__ __forceinline__ void stage_mn(const uint16_t* __restrict__ g, int64_t
     const int q = i * NW + wave;
     const int lin = q * 64 + lane;
     const int row = lin / CPR;
-    const int lc = (lin % CPR) ^ (mn_swz(row) & (CPR - 1));
+    const int lc = (lin % CPR) ^ mn_swz_r<R>(row);
     int gc = c0 + lc * 8;
     gc = gc < cmax ? gc : cmax - 8;
     const int kr = k0 + row;
     const uint16_t* src = kr < kend ? g + (int64_t)kr * ld + gc : zero;
     glds16(src, img + q * 1024);
   }
-}
-
-template <int R, bool KMAJ>
-__device__ __forceinline__ bf16x8_t frag(const char* img, int rbase, int s, int lane) {
-  Frag8 f;
-  if constexpr (KMAJ) {
-    const int row = rbase + (lane & 15);
-    const int c = s * 4 + (lane >> 4);
-    f.u = *reinterpret_cast<const uint4*>(img + row * 128 + ((c ^ ((row >> 1) & 7)) << 4));
-  } else {
-    const int g = lane >> 4, i = lane & 15, q = i >> 2, pp = i & 3;
-    const int col = rbase + pp * 4;
-    const int lc = col >> 3, sub = (col & 7) * 2;
-    const int k1 = s * 32 + g * 8 + q, k2 = k1 + 4;
-    f.h[0] = lds_tr(img + k1 * (R * 2) + ((lc ^ (mn_swz(k1) & (R / 8 - 1))) << 4) + sub);
-    f.h[1] = lds_tr(img + k2 * (R * 2) + ((lc ^ (mn_swz(k2) & (R / 8 - 1))) << 4) + sub);
-  }
-  return f.v;
 }
 
 // BM x BN tile, NW waves as 2 (M) x NW/2 (N); per wave (BM/2) x (2 BN/NW) = MR x NR fragments of 16 x 16
@@ -168,9 +115,9 @@ __global__ __launch_bounds__(NW * 64, (BM * BN > 128 * 128 ? 1 : 2)) void groupe
   auto stage_tile = [&](int t, int buf) {
     char* base = smem + buf * STAGE;
     const int k0 = kbeg + t * kK;
-    if constexpr (AK) stage_k<BM, NW>(p.a, p.lda, m0, mend, k0, base, wave, lane);
+    if constexpr (AK) stage<BM, true, NW>(p.a, p.lda, m0, mend, k0, base, wave, lane);
     else stage_mn<BM, NW>(p.a, p.lda, m0, mend, k0, kend, p.zero, base, wave, lane);
-    if constexpr (BK) stage_k<BN, NW>(bptr, p.ldb, n0, p.N, k0, base + A_BYTES, wave, lane);
+    if constexpr (BK) stage<BN, true, NW>(bptr, p.ldb, n0, p.N, k0, base + A_BYTES, wave, lane);
     else stage_mn<BN, NW>(bptr, p.ldb, n0, p.N, k0, MODE == 2 ? kend : k0 + kK, p.zero, base + A_BYTES, wave, lane);
   };
 
