@@ -6,7 +6,8 @@
 // A and B are both K-major (x [M][K] and the weight stored [N][K], transpose_y=True in the reference);
 // the Python wrapper makes other layouts K-major first. Either operand may be e4m3 or e5m2
 // (cbsz / blgp format codes 0 / 1). The per-tensor scale of the reference is `alpha`, applied in the
-// epilogue; the MFMA's per-32-element E8M0 block scales are all 1.0 (exponent 127), so the
+// epilogue, times the operands' scale inverses read from device memory when given (pa_gemm_fp8_dscale: the
+// scales quant_fp8.hip computes on the device never cross to the host); the MFMA's per-32-element E8M0 block scales are all 1.0 (exponent 127), so the
 // instruction runs the MX-fp8 rate (2x bf16 per clock) on plain per-tensor-scaled data.
 //
 // Structure: the bf16 generic kernel's (gemm.hip gemm_bf16_kernel) at the same bytes: 256 x 256 tiles,
@@ -42,6 +43,10 @@ struct Fp8Args {
   int tiles_m, tiles_n;
   float alpha;
   int act;  // 0 identity, 1 gelu (erf), 2 relu
+  // per-tensor dequantisation scales in device memory (one fp32 each, or null = 1): the epilogues multiply alpha by
+  // them, so a scale computed on the device never crosses to the host
+  const float* a_scale_inv;
+  const float* b_scale_inv;
   // balanced tail (ping-pong kernel, as gemm.hip's): tiles [full_tiles, tiles) are cut along K into tail_split
   // slices that write fp32 256 x 256 partials to tail_ws; gemm_fp8_tail_reduce_k sums them and applies the epilogue
   int full_tiles, tail_split;
@@ -60,6 +65,11 @@ __device__ __forceinline__ i32x8 frag(const char* img, int rbase, int lane) {
   f[0] = (int)lo.x; f[1] = (int)lo.y; f[2] = (int)lo.z; f[3] = (int)lo.w;
   f[4] = (int)hi.x; f[5] = (int)hi.y; f[6] = (int)hi.z; f[7] = (int)hi.w;
   return f;
+}
+
+// alpha times the device-side scales, formed once per workgroup before its epilogue loop (null pointers: alpha itself)
+__device__ __forceinline__ float alpha_eff(const Fp8Args& p) {
+  return p.alpha * (p.a_scale_inv ? *p.a_scale_inv : 1.f) * (p.b_scale_inv ? *p.b_scale_inv : 1.f);
 }
 
 __device__ __forceinline__ float act_f(float v, int act) {
@@ -123,6 +133,7 @@ __global__ __launch_bounds__(512, 1) void gemm_fp8_kernel(Fp8Args p) {
   // lane holds C[m = mrow0 + i*16][n = ncol0 + j*16 + 0..3]
   const int mrow0 = m0 + wm * 128 + (lane & 15);
   const int ncol0 = n0 + wn * 64 + 4 * (lane >> 4);
+  const float alpha = alpha_eff(p);
 #pragma unroll
   for (int j = 0; j < NR; ++j) {
     const int n = ncol0 + j * 16;
@@ -142,7 +153,7 @@ __global__ __launch_bounds__(512, 1) void gemm_fp8_kernel(Fp8Args p) {
       if (m >= p.M) continue;
       float v[4];
 #pragma unroll
-      for (int e = 0; e < 4; ++e) v[e] = act_f(acc[i][j][e] * p.alpha + bv[e], p.act);
+      for (int e = 0; e < 4; ++e) v[e] = act_f(acc[i][j][e] * alpha + bv[e], p.act);
       uint2* cp = reinterpret_cast<uint2*>(reinterpret_cast<uint16_t*>(p.c) + (int64_t)m * p.ldc + n);
       *cp = OUT_F16 ? make_uint2(pack_f16(v[0], v[1]), pack_f16(v[2], v[3]))
                     : make_uint2(pack_bf16(v[0], v[1]), pack_bf16(v[2], v[3]));
@@ -208,9 +219,10 @@ __global__ __launch_bounds__(256) void gemm_fp8_tail_reduce_k(Fp8Args p) {
     }
   }
   const float av[4] = {a.x, a.y, a.z, a.w};
+  const float alpha = alpha_eff(p);
   float v[4];
 #pragma unroll
-  for (int q = 0; q < 4; ++q) v[q] = act_f(av[q] * p.alpha + bq[q], p.act);
+  for (int q = 0; q < 4; ++q) v[q] = act_f(av[q] * alpha + bq[q], p.act);
   *reinterpret_cast<uint2*>(reinterpret_cast<uint16_t*>(p.c) + (int64_t)m * p.ldc + n) =
       OUT_F16 ? make_uint2(pack_f16(v[0], v[1]), pack_f16(v[2], v[3]))
               : make_uint2(pack_bf16(v[0], v[1]), pack_bf16(v[2], v[3]));
@@ -398,6 +410,7 @@ __global__ __launch_bounds__(kPPThreads, 1) void gemm_fp8_pp_kernel(Fp8Args p) {
   asm volatile("s_nop 7\n\ts_nop 7\n\ts_nop 7" ::: "memory");
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   uint16_t* im = reinterpret_cast<uint16_t*>(smem);
+  const float alpha = alpha_eff(p);
   bar();
 #pragma unroll
   for (int bh = 0; bh < 2; ++bh)
@@ -420,7 +433,7 @@ __global__ __launch_bounds__(kPPThreads, 1) void gemm_fp8_pp_kernel(Fp8Args p) {
           const int r = ah * 128 + ar + i * 16 + (lane & 15);
           float v[4];
 #pragma unroll
-          for (int e = 0; e < 4; ++e) v[e] = act_f(acc[ah][i][bh][j][e] * p.alpha + bq[e], p.act);
+          for (int e = 0; e < 4; ++e) v[e] = act_f(acc[ah][i][bh][j][e] * alpha + bq[e], p.act);
           *reinterpret_cast<uint2*>(im + r * kEpiRS + c) =
               OUT_F16 ? make_uint2(pack_f16(v[0], v[1]), pack_f16(v[2], v[3]))
                       : make_uint2(pack_bf16(v[0], v[1]), pack_bf16(v[2], v[3]));
@@ -477,24 +490,36 @@ PA_EXPORT int64_t pa_gemm_fp8_ws_bytes(int64_t M, int64_t N, int64_t K) {
 
 static int fp8_impl(const void* a, const void* b, void* c, const void* bias, int64_t M, int64_t N, int64_t K,
                     int64_t lda, int64_t ldb, int64_t ldc, int fmt_a, int fmt_b, float alpha, int act, int out_f16,
-                    void* ws, hipStream_t st);
+                    void* ws, const float* a_scale_inv, const float* b_scale_inv, hipStream_t st);
 
 PA_EXPORT int pa_gemm_fp8(const void* a, const void* b, void* c, const void* bias, int64_t M, int64_t N, int64_t K,
                           int64_t lda, int64_t ldb, int64_t ldc, int fmt_a, int fmt_b, float alpha, int act,
                           int out_f16, hipStream_t st) {
-  return fp8_impl(a, b, c, bias, M, N, K, lda, ldb, ldc, fmt_a, fmt_b, alpha, act, out_f16, nullptr, st);
+  return fp8_impl(a, b, c, bias, M, N, K, lda, ldb, ldc, fmt_a, fmt_b, alpha, act, out_f16, nullptr, nullptr, nullptr,
+                  st);
 }
 
 // the same with the balanced-tail workspace (pa_gemm_fp8_ws_bytes(M, N, K) bytes; may be null when that is 0)
 PA_EXPORT int pa_gemm_fp8_ws(const void* a, const void* b, void* c, const void* bias, int64_t M, int64_t N, int64_t K,
                              int64_t lda, int64_t ldb, int64_t ldc, int fmt_a, int fmt_b, float alpha, int act,
                              int out_f16, void* ws, hipStream_t st) {
-  return fp8_impl(a, b, c, bias, M, N, K, lda, ldb, ldc, fmt_a, fmt_b, alpha, act, out_f16, ws, st);
+  return fp8_impl(a, b, c, bias, M, N, K, lda, ldb, ldc, fmt_a, fmt_b, alpha, act, out_f16, ws, nullptr, nullptr,
+                  st);
+}
+
+// pa_gemm_fp8_ws with the operands' dequantisation scales read from device memory: C = act(alpha * *a_scale_inv *
+// *b_scale_inv * A . B^T + bias); either pointer may be null (= 1)
+PA_EXPORT int pa_gemm_fp8_dscale(const void* a, const void* b, void* c, const void* bias, int64_t M, int64_t N,
+                                 int64_t K, int64_t lda, int64_t ldb, int64_t ldc, int fmt_a, int fmt_b, float alpha,
+                                 int act, int out_f16, void* ws, const float* a_scale_inv, const float* b_scale_inv,
+                                 hipStream_t st) {
+  return fp8_impl(a, b, c, bias, M, N, K, lda, ldb, ldc, fmt_a, fmt_b, alpha, act, out_f16, ws, a_scale_inv,
+                  b_scale_inv, st);
 }
 
 static int fp8_impl(const void* a, const void* b, void* c, const void* bias, int64_t M, int64_t N, int64_t K,
                     int64_t lda, int64_t ldb, int64_t ldc, int fmt_a, int fmt_b, float alpha, int act, int out_f16,
-                    void* ws, hipStream_t st) {
+                    void* ws, const float* a_scale_inv, const float* b_scale_inv, hipStream_t st) {
   if (K % kKB != 0 || N % 4 != 0 || lda % 16 != 0 || ldb % 16 != 0 || ldc % 4 != 0) return 1;
   if (fmt_a < 0 || fmt_a > 1 || fmt_b < 0 || fmt_b > 1 || act < 0 || act > 2) return 1;
   if (M <= 0 || N <= 0) return 0;
@@ -505,6 +530,7 @@ static int fp8_impl(const void* a, const void* b, void* c, const void* bias, int
   g.tiles_m = (int)((M + kTile - 1) / kTile);
   g.tiles_n = (int)((N + kTile - 1) / kTile);
   g.alpha = alpha; g.act = act;
+  g.a_scale_inv = a_scale_inv; g.b_scale_inv = b_scale_inv;
   const bool pp = g_fp8_kernel != 1 && N % 8 == 0 && ldc % 8 == 0;
   TailPlan pl = tail_plan(M, N, K, kKB, device_cus());
   if (!pp || !ws) pl = without_tail(pl);

@@ -21,6 +21,64 @@ class FusedLinear(_nn.Layer):
         return F.fused_linear(x, self.weight, self.bias, self.transpose_weight)
 
 
+class FP8Linear(_nn.Layer):
+    """nn.Linear on the fp8 GEMM (F.fp8_linear): same parameters (weight [in, out], bias [out]); the forward product
+    and both backward products read fp8 operands with per-tensor scales. ``recipe``: "delayed" (scale from the
+    maximum of the last ``amax_history_len`` amaxes; one pass per tensor) or "current" (scale from the tensor itself;
+    one more read of it). ``margin``: the scale is lowered by 2^-margin. The scaling states of the three quantized
+    roles (input, weight, output gradient) are buffers — fp8_{x,w,dy}_{amax_history,scale,scale_inv} — and travel
+    with state_dict. Reference: none in Paddle 3.0; the project's own name."""
+
+    _ROLES = (("x", "float8_e4m3fn"), ("w", "float8_e4m3fn"), ("dy", "float8_e5m2"))
+
+    def __init__(self, in_features, out_features, weight_attr=None, bias_attr=None, recipe="delayed",
+                 amax_history_len=16, margin=0, name=None, _share=None):
+        super().__init__()
+        import torch
+        from ...framework.tensor import _wrap
+        from ...ops import fp8 as _f8
+        self._in_features, self._out_features = in_features, out_features
+        if _share is None:
+            self.weight = self.create_parameter([in_features, out_features], attr=weight_attr, is_bias=False)
+            self.bias = self.create_parameter([out_features], attr=bias_attr, is_bias=True)
+        else:
+            self.weight, self.bias = _share
+        self.recipe, self.amax_history_len, self.margin, self.name = recipe, amax_history_len, margin, name
+        dev = self.weight._t.device
+        states = {}
+        for role, fmt in self._ROLES:
+            bufs = []
+            for suffix, init in (("amax_history", torch.zeros(amax_history_len)), ("scale", torch.ones(1)),
+                                 ("scale_inv", torch.ones(1))):
+                b = _wrap(init.to(dev))
+                self.register_buffer(f"fp8_{role}_{suffix}", b)
+                bufs.append(b)
+            states[role] = _f8.Fp8TensorState(fmt, recipe, amax_history_len, margin, buffers=tuple(bufs))
+        object.__setattr__(self, "_fp8_states", states)
+
+    @classmethod
+    def from_linear(cls, layer, recipe="delayed", amax_history_len=16, margin=0):
+        """An FP8Linear over the parameters of an existing nn.Linear (shared, not copied)."""
+        k, n = layer.weight.shape
+        return cls(k, n, recipe=recipe, amax_history_len=amax_history_len, margin=margin,
+                   _share=(layer.weight, layer.bias))
+
+    def _after_set_state_dict(self):
+        # a loaded state that has seen a tensor continues by its recipe; an empty one starts over (load time only)
+        for st in self._fp8_states.values():
+            st.calls = 1 if bool((st.amax_history != 0).any()) else 0
+            st.cache = None
+
+    def forward(self, x):
+        if x.dtype != self.weight.dtype:
+            x = x.astype(self.weight.dtype)
+        return F.fp8_linear(x, self.weight, self.bias, self._fp8_states)
+
+    def extra_repr(self):
+        return (f"in_features={self._in_features}, out_features={self._out_features}, recipe={self.recipe}, "
+                f"dtype={self._dtype}")
+
+
 class FusedDropoutAdd(_nn.Layer):
     def __init__(self, p=0.5, mode="upscale_in_train", name=None):
         super().__init__()

@@ -211,6 +211,43 @@ def fused_linear(x, weight, bias=None, transpose_weight=False, name=None):
     return fused_matmul_bias(x, weight, bias, False, transpose_weight)
 
 
+def fp8_quantize(x, dtype="float8_e4m3fn", scale=None, return_transpose=False, margin=0):
+    """Per-tensor scaled fp8 quantization: q = sat(x * scale) in ``dtype`` (float8_e4m3fn / float8_e5m2, OCP).
+    Returns (q, scale_inv) or (q, scale_inv, qT) with qT = q viewed as [rows, last dim] transposed. ``scale`` None:
+    current scaling, scale = (fmax / |x|max) * 2^-margin computed on the device (1 for an all-zero x); else a number
+    or a one-element tensor. On the device one HIP pass (csrc/kernels/quant_fp8.hip) writes q and qT.
+    Reference: none in Paddle 3.0, which publishes only fp8_fp8_half_gemm_fused; this name is the project's own."""
+    from ...ops import fp8 as _f8
+    xt = _t(x)
+    fmt = _f8._fmt_of(dtype if isinstance(dtype, str) else _dt_name(dtype))
+    if scale is None:
+        st = _f8.Fp8TensorState(fmt, "current", 1, margin, xt.device)
+        q, qT, sinv = st.quantize(xt, transpose=return_transpose)
+    else:
+        sc = _t(scale) if isinstance(scale, Tensor) else torch.as_tensor(float(scale))
+        sc = sc.detach().to(device=xt.device, dtype=torch.float32).reshape(1)
+        q, qT = _f8.quantize_fp8(xt, fmt, sc, return_transpose)
+        sinv = 1.0 / sc
+    return (_wrap(q), _wrap(sinv), _wrap(qT)) if return_transpose else (_wrap(q), _wrap(sinv))
+
+
+def _dt_name(d):
+    from ...framework import dtype as _dt
+    return d if isinstance(d, torch.dtype) else _dt.convert_dtype(d).name
+
+
+def fp8_linear(x, weight, bias=None, state=None):
+    """y = x @ weight + bias (weight [in, out]) with the forward and both backward products on the fp8 GEMM:
+    x and weight quantized to e4m3fn, the output gradient to e5m2, per-tensor scales kept on the device.
+    ``state``: the {"x", "w", "dy"} scaling states of ops.fp8.new_states() (FP8Linear owns one set); None = current
+    scaling. Shapes the fp8 GEMM does not take (rows, in or out not a multiple of 128; not bf16 / fp16) run the
+    ordinary fused linear and count in ops.fp8.CALLS["fallback"]; off the device the same quantization is emulated
+    with fp32 products. Reference: none in Paddle 3.0; the project's own name."""
+    from ...ops import fp8 as _f8
+    xt = _t(x)
+    return _wrap(_f8.fp8_linear(xt, _t(weight), _t(bias), state, emulate=not xt.is_cuda))
+
+
 def fused_linear_activation(x, y, bias, trans_x=False, trans_y=False, activation=None):
     act = {None: None, "none": None, "gelu": "gelu", "relu": "relu"}[activation]
     xt, w = _t(x), _t(y)

@@ -398,6 +398,10 @@ class Layer:
         for k in state_dict:
             if k not in mapping:
                 unexpected.append(k)
+        for l in self.sublayers(include_self=True):  # layers that keep host-side state derived from their buffers
+            after = getattr(l, "_after_set_state_dict", None)
+            if after is not None:
+                after()
         return missing, unexpected
 
     set_dict = set_state_dict

@@ -87,6 +87,13 @@ SIGS = {
     "pa_gemm_fp8_set_kernel": [_i32],
     "pa_gemm_fp8_ws": [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _i32, _i32, _f32, _i32, _i32, _vp, _vp],
     "pa_gemm_fp8_ws_bytes": [_i64, _i64, _i64],
+    "pa_gemm_fp8_dscale": [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _i32, _i32, _f32, _i32, _i32, _vp,
+                           _vp, _vp, _vp],
+    # fp8 quantisation (quant_fp8.hip)
+    "pa_fp8_nparts": [],
+    "pa_fp8_amax": [_vp, _i64, _i32, _vp, _vp],
+    "pa_fp8_scale_update": [_vp, _i32, _vp, _i32, _vp, _vp, _f32, _i32, _i32, _vp],
+    "pa_fp8_quant": [_vp, _i64, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _vp],
     "pa_gemm_bf16_4w_abl": [_vp, _vp, _vp, _i64, _i64, _i64, _i32, _vp],
     "pa_gemm_small_m": [_vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp],
     "pa_gemm_skinny": [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _i32, _i32, _vp],
@@ -143,5 +150,5 @@ SIGS = {
     "pa_version": [],
 }
 
-RET_I64 = {"pa_flash_attn_bwd_ds_bytes", "pa_gemm_pp_ws_bytes", "pa_gemm_fp8_ws_bytes", "pa_gemm_pp_splitk_ws_bytes", "pa_bn_pre_ws", "pa_gemm_skinny_stats_chunks", "pa_conv_skinny_stats_chunks",
+RET_I64 = {"pa_fp8_nparts", "pa_flash_attn_bwd_ds_bytes", "pa_gemm_pp_ws_bytes", "pa_gemm_fp8_ws_bytes", "pa_gemm_pp_splitk_ws_bytes", "pa_bn_pre_ws", "pa_gemm_skinny_stats_chunks", "pa_conv_skinny_stats_chunks",
            "pa_colsum_nparts", "pa_multi_tensor_chunk"}
