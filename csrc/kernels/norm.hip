@@ -82,11 +82,19 @@ __global__ __launch_bounds__(256) void norm_fwd_rows(const T* __restrict__ x, co
   }
 }
 
-// wide rows (>= 4096 columns): one 256-thread workgroup per row, two passes over global (the second hits L2).
+// wide rows (> 3072 columns): one 256-thread workgroup per row, two passes over global (the second hits L2).
 // Measured in the GPT-3 13B step (5120 columns, operands from HBM): forward 19.5 vs 22.5 us, data gradient 38.8 vs
 // 48.0 us for the wave-per-row kernels (`profiles/norm_rows_vs_wide_r4.md`): a whole workgroup's loads per row in
-// flight instead of one wave's. LayerNorm sums are taken about the row's first element (shifted moments) so the
-// one-pass variance does not cancel for rows with a large mean.
+// flight instead of one wave's.
+// LayerNorm statistics in the one pass, without a subtraction that can cancel: each 8-element vector gives its own
+// mean and its sum of squared deviations from that mean (both from registers), a thread folds its vectors into
+// (count, mean, M2) with the pairwise update M2 += q + delta^2 * na * nb / (na + nb), and the workgroup combines the
+// threads the same way in two sums: the row mean from the thread means, then M2 + count * (thread mean - row mean)^2.
+// Every term is a square, so neither a large row mean nor an outlier anywhere in the row costs the variance its
+// digits (one-pass moments about x[0], var = s2/n - md^2, lost them whenever x[0] was far from the row mean:
+// `profiles/layer_norm_wide_outlier.md`). The thread means are summed about x[0] only to keep the digits of the
+// mean of a row with a large mean; an outlier x[0] costs that sum ~ulp(x[0]) per thread, nothing against the
+// spread such a row has.
 template <typename T, bool LN>
 __global__ __launch_bounds__(256) void norm_fwd_wide(const T* __restrict__ x, const T* __restrict__ w,
                                                      const T* __restrict__ b, T* __restrict__ y,
@@ -95,22 +103,34 @@ __global__ __launch_bounds__(256) void norm_fwd_wide(const T* __restrict__ x, co
   __shared__ float red[4];
   const int64_t row = blockIdx.x;
   const T* xr = x + row * cols;
-  const float sh = LN ? to_f(xr[0]) : 0.f;
-  float s = 0.f, s2 = 0.f;
+  float s2 = 0.f;                           // RMSNorm: sum of squares
+  float cnt = 0.f, mt = 0.f, m2 = 0.f;      // LayerNorm: count, mean and sum of squared deviations of this thread's elements
   for (int64_t e = (int64_t)threadIdx.x * 8; e < cols; e += 256 * 8) {
     float v[8];
     load8<T>(xr + e, v);
+    if (LN) {
+      float g = 0.f, q = 0.f;
 #pragma unroll
-    for (int j = 0; j < 8; ++j) { const float d = v[j] - sh; s += d; s2 += d * d; }
+      for (int j = 0; j < 8; ++j) g += v[j];
+      const float m8 = g * 0.125f;
+#pragma unroll
+      for (int j = 0; j < 8; ++j) { const float d = v[j] - m8; q += d * d; }
+      const float dl = m8 - mt, r = 8.f * __builtin_amdgcn_rcpf(cnt + 8.f);
+      mt += dl * r;
+      m2 += q + dl * dl * cnt * r;
+      cnt += 8.f;
+    } else {
+#pragma unroll
+      for (int j = 0; j < 8; ++j) s2 += v[j] * v[j];
+    }
   }
   const float inv_n = 1.0f / (float)cols;
   float mu = 0.f, rstd;
   if (LN) {
-    s = block_sum<256>(s, red);
-    s2 = block_sum<256>(s2, red);
-    const float md = s * inv_n;
-    mu = sh + md;
-    rstd = rsqrtf(fmaxf(s2 * inv_n - md * md, 0.f) + eps);
+    const float x0 = to_f(xr[0]);
+    mu = x0 + block_sum<256>(cnt * (mt - x0), red) * inv_n;
+    const float dm = mt - mu;
+    rstd = rsqrtf(block_sum<256>(m2 + cnt * dm * dm, red) * inv_n + eps);
   } else {
     s2 = block_sum<256>(s2, red);
     rstd = rsqrtf(s2 * inv_n + eps);
@@ -249,6 +269,7 @@ __global__ __launch_bounds__(256) void norm_bwd_wb(const T* __restrict__ dy, con
 template <typename T, bool LN>
 int launch_fwd(const void* x, const void* w, const void* b, void* y, float* mean, float* rstd, int64_t rows,
                int64_t cols, float eps, hipStream_t st) {
+  if (rows <= 0 || cols <= 0) return 0;
   const int64_t vpl = cdiv(cols, 512);
   dim3 grid((unsigned)cdiv(rows, 4)), block(256);
   auto X = (const T*)x; auto W = (const T*)w; auto B = (const T*)b; auto Y = (T*)y;
@@ -268,11 +289,15 @@ template <typename T, bool LN>
 int launch_bwd(const void* dy, const void* x, const void* w, const float* mean, const float* rstd, void* dx,
                float* dw_part, float* db_part, int64_t rows, int64_t cols, int nparts, hipStream_t st,
                const void* res = nullptr) {
+  if (cols <= 0) return 0;
   const int64_t vpl = cdiv(cols, 512);
   dim3 grid((unsigned)cdiv(rows, 4)), block(256);
   auto DY = (const T*)dy; auto X = (const T*)x; auto W = (const T*)w; auto DX = (T*)dx; auto RES = (const T*)res;
 #define PA_BWD(V) hipLaunchKernelGGL((norm_bwd_dx_rows<T, V, LN>), grid, block, 0, st, DY, X, W, mean, rstd, DX, rows, cols, RES)
-  if (vpl <= 1) PA_BWD(1);
+  // no rows: no dx launch (an empty grid is a launch error), but norm_bwd_wb below still runs and writes the zero
+  // column sums into the partials
+  if (rows <= 0) {}
+  else if (vpl <= 1) PA_BWD(1);
   else if (vpl <= 2) PA_BWD(2);
   else if (vpl <= 3) PA_BWD(3);
   else if (vpl <= 4) PA_BWD(4);

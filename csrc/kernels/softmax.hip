@@ -11,11 +11,14 @@ using namespace pa;
 
 namespace {
 
+// (max, sum of exp(x - max)) of a set of elements. A set that is empty or -inf everywhere is {-inf, 0}: its sum
+// must be 0, not exp(-inf - -inf) = NaN, or NaN * exp(-inf) = NaN would poison a finite partner in the merge.
 struct MS { float m, s; };
 
 __device__ __forceinline__ MS ms_merge(MS a, MS b) {
   const float m = fmaxf(a.m, b.m);
   if (m == -INFINITY) return {m, 0.f};
+  // the side whose max is -inf carries s = 0 and exp(-inf - m) = 0: it adds exactly 0
   return {m, a.s * __expf(a.m - m) + b.s * __expf(b.m - m)};
 }
 
@@ -49,9 +52,12 @@ __device__ __forceinline__ MS row_stats(const T* xr, int64_t cols) {
     float m = v[0];
 #pragma unroll
     for (int j = 1; j < 8; ++j) m = fmaxf(m, v[j]);
+    // a group that is -inf everywhere (masked positions, banned tokens): subtract 0 so that every term is
+    // exp(-inf) = 0 and the group is {-inf, 0}
+    const float mz = m == -INFINITY ? 0.f : m;
     float s = 0.f;
 #pragma unroll
-    for (int j = 0; j < 8; ++j) s += __expf(v[j] - m);
+    for (int j = 0; j < 8; ++j) s += __expf(v[j] - mz);
     acc = ms_merge(acc, MS{m, s});
   }
   return acc;
@@ -192,6 +198,7 @@ __global__ __launch_bounds__(256) void ce_slice_bwd_k(const T* logits, const int
 }  // namespace
 
 PA_EXPORT int pa_softmax_fwd(const void* x, void* y, int64_t rows, int64_t cols, int dtype, hipStream_t st) {
+  if (rows <= 0) return 0;
   PA_DISPATCH_DTYPE(dtype, T, hipLaunchKernelGGL((softmax_fwd_k<T>), dim3((unsigned)rows), dim3(256), 0, st,
                                                  (const T*)x, (T*)y, cols));
   PA_CHECK_LAUNCH();
@@ -200,6 +207,7 @@ PA_EXPORT int pa_softmax_fwd(const void* x, void* y, int64_t rows, int64_t cols,
 
 PA_EXPORT int pa_softmax_bwd(const void* y, const void* dy, void* dx, int64_t rows, int64_t cols, int dtype,
                              hipStream_t st) {
+  if (rows <= 0) return 0;
   PA_DISPATCH_DTYPE(dtype, T, hipLaunchKernelGGL((softmax_bwd_k<T>), dim3((unsigned)rows), dim3(256), 0, st,
                                                  (const T*)y, (const T*)dy, (T*)dx, cols));
   PA_CHECK_LAUNCH();
@@ -208,6 +216,7 @@ PA_EXPORT int pa_softmax_bwd(const void* y, const void* dy, void* dx, int64_t ro
 
 PA_EXPORT int pa_softmax_ce_fwd(const void* logits, const int64_t* labels, float* loss, float* lse, int64_t rows,
                                 int64_t cols, int64_t ignore_index, int dtype, hipStream_t st) {
+  if (rows <= 0) return 0;
   PA_DISPATCH_DTYPE(dtype, T, hipLaunchKernelGGL((softmax_ce_fwd_k<T>), dim3((unsigned)rows), dim3(256), 0, st,
                                                  (const T*)logits, labels, loss, lse, cols, ignore_index));
   PA_CHECK_LAUNCH();
@@ -217,6 +226,7 @@ PA_EXPORT int pa_softmax_ce_fwd(const void* logits, const int64_t* labels, float
 PA_EXPORT int pa_softmax_ce_bwd(const void* logits, const int64_t* labels, const float* lse, const float* dloss,
                                 void* dlogits, int64_t rows, int64_t cols, int64_t ignore_index, int dtype,
                                 hipStream_t st) {
+  if (rows <= 0) return 0;
   PA_DISPATCH_DTYPE(dtype, T, hipLaunchKernelGGL((softmax_ce_bwd_k<T>), dim3((unsigned)rows), dim3(256), 0, st,
                                                  (const T*)logits, labels, lse, dloss, (T*)dlogits, cols,
                                                  ignore_index));

@@ -58,14 +58,19 @@ def softmax_cross_entropy(logits, labels, ignore_index=-100):
 # ---------------------------------------------------------------------------------------------
 # Cross entropy over a vocabulary slice [v0, v0 + V) (vocab-parallel CE, vocab-chunked LM head):
 # per-row logsumexp and label logit of the slice; the gradient with the global logsumexp.
+def _labels_i64(labels1d):
+    """The kernels read the labels as one dense int64 vector: int32 labels or a strided view are converted."""
+    return labels1d.contiguous().view(-1).to(torch.int64)
+
+
 def ce_slice_stats(logits2d, labels1d, v0):
     """(lse [rows] fp32, label logit [rows] fp32, 0 when the label is outside the slice)."""
     rows, V = logits2d.shape
     if L.hip_enabled_for(logits2d) and logits2d.dtype in L._DT and V % 8 == 0 and logits2d.is_contiguous():
         lse = torch.empty(rows, dtype=torch.float32, device=logits2d.device)
         tgt = torch.empty(rows, dtype=torch.float32, device=logits2d.device)
-        L.call("pa_ce_slice_fwd", L.ptr(logits2d), L.ptr(labels1d), L.ptr(lse), L.ptr(tgt), rows, V, int(v0),
-               L.dcode(logits2d), L.stream_ptr())
+        L.call("pa_ce_slice_fwd", L.ptr(logits2d), L.ptr(_labels_i64(labels1d)), L.ptr(lse), L.ptr(tgt), rows, V,
+               int(v0), L.dcode(logits2d), L.stream_ptr())
         return lse, tgt
     lf = logits2d.float()
     local = labels1d - v0
@@ -81,8 +86,9 @@ def ce_slice_grad(logits2d, labels1d, v0, lse, dloss, ignore_index, out=None):
         out = torch.empty_like(logits2d)
     if L.hip_enabled_for(logits2d) and logits2d.dtype in L._DT and V % 8 == 0 and logits2d.is_contiguous() \
             and out.is_contiguous():
-        L.call("pa_ce_slice_bwd", L.ptr(logits2d), L.ptr(labels1d), L.ptr(lse), L.ptr(dloss.float().contiguous()),
-               L.ptr(out), rows, V, int(v0), int(ignore_index), L.dcode(logits2d), L.stream_ptr())
+        L.call("pa_ce_slice_bwd", L.ptr(logits2d), L.ptr(_labels_i64(labels1d)), L.ptr(lse),
+               L.ptr(dloss.float().contiguous()), L.ptr(out), rows, V, int(v0), int(ignore_index),
+               L.dcode(logits2d), L.stream_ptr())
         return out
     p = torch.exp(logits2d.float() - lse.unsqueeze(-1))
     local = labels1d - v0

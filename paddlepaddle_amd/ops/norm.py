@@ -2,7 +2,7 @@
 
 Reference: paddle/phi/kernels/gpu/rms_norm_kernel.cu, layer_norm_kernel.cu,
 python/paddle/incubate/nn/functional/fused_rms_norm.py.
-Kernels: csrc/kernels/norm.hip — one 64-lane wave per row for hidden ≤ 8192 (vectorised
+Kernels: csrc/kernels/norm.hip — one 64-lane wave per row for hidden ≤ 3072 (vectorised
 16-byte loads, fp32 statistics kept in registers), block-per-row above that.
 """
 from __future__ import annotations

@@ -34,8 +34,6 @@ def test_rms_norm(dt, cols):
     torch.manual_seed(0)
     x = torch.randn(37, cols, device=DEV, dtype=dt, requires_grad=True)
     w = (torch.rand(cols, device=DEV) + 0.5).to(dt).requires_grad_(True)
-    if cols % 8:
-        pytest.skip("cols must be a multiple of 8 for the HIP path")
     y = ops.rms_norm(x, w, 1e-6)
     _lib_loaded("pa_rms_norm_fwd")
     xr, wr = x.detach().float().requires_grad_(True), w.detach().float().requires_grad_(True)
@@ -54,7 +52,7 @@ def test_rms_norm(dt, cols):
                                         (5120, 300.0), (3072, 300.0)])
 def test_layer_norm(dt, cols, shift):
     """Wave-per-row kernels up to 3072 columns, workgroup-per-row kernels above; shift = 300: rows whose mean is
-    large against their spread (the wide kernel's shifted moments must not cancel)."""
+    large against their spread (the wide kernel's one-pass statistics must not cancel)."""
     torch.manual_seed(1)
     x = (torch.randn(29, cols, device=DEV) * 3 + shift).to(dt).requires_grad_(True)
     w = torch.randn(cols, device=DEV).to(dt).requires_grad_(True)
@@ -96,6 +94,7 @@ def test_norm_without_affine_params(op):
 @pytest.mark.parametrize("dt", [torch.float32, torch.bfloat16])
 @pytest.mark.parametrize("cols", [8, 128, 4096, 50304])
 def test_softmax(dt, cols):
+    torch.manual_seed(4)
     x = (torch.randn(13, cols, device=DEV) * 4).to(dt).requires_grad_(True)
     y = ops.softmax(x, -1)
     _lib_loaded("pa_softmax_fwd")
