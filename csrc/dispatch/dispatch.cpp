@@ -1,8 +1,10 @@
 // Native launch path for the HIP kernel library (_C_hip.so).
 //
-// Every exported launcher `pa_*` gets a METH_FASTCALL CPython entry point generated from the signature
-// table in paddlepaddle_amd/ops/_loader.py (tools/build_native.py writes dispatch_gen.inc). An entry point
-// unpacks its arguments straight from the Python objects the op layer already holds:
+// Every exported launcher `pa_*` gets a METH_FASTCALL CPython entry point: one instantiation of entry<&pa_xxx>,
+// which reads the parameter types off the declaration in csrc/kernels/pa_api.h. dispatch_gen.inc (written by
+// tools/build_native.py from the ctypes table paddlepaddle_amd/ops/_sigs.py) lists the launchers with the signature
+// code the table gives them; a row that disagrees with pa_api.h, or names no declared launcher, fails the build.
+// An entry point unpacks its arguments straight from the Python objects the op layer already holds:
 //   pointer args : torch.Tensor (-> data_ptr), None (-> nullptr), int, a ctypes pointer / struct, or the
 //                  current-stream sentinel (-> the caller's current HIP stream, read from c10 without
 //                  creating a Python stream object),
@@ -16,6 +18,12 @@
 #include <torch/csrc/autograd/python_variable.h>
 
 #include <cstdint>
+#include <tuple>
+#include <utility>
+#include <vector>
+
+#include "pa_api.h"
+#include "sig_code.h"
 
 namespace {
 
@@ -131,11 +139,61 @@ PyObject* bad_nargs(const char* name, Py_ssize_t want, Py_ssize_t got) {
   return nullptr;
 }
 
-}  // namespace
+// argument `o` as a parameter of type T; the converter goes by T's signature code (sig_code.h)
+template <typename T> bool arg_as(PyObject* o, T* out) {
+  constexpr char k = pa_sig::code<T>();
+  if constexpr (k == 'p') {
+    void* p;
+    if (!arg_ptr(o, &p)) return false;
+    *out = static_cast<T>(p);
+    return true;
+  } else if constexpr (k == 'l') {
+    return arg_i64(o, out);
+  } else if constexpr (k == 'i') {
+    return arg_i32(o, out);
+  } else if constexpr (k == 'u') {
+    return arg_u64(o, out);
+  } else {
+    static_assert(k == 'f');
+    return arg_f32(o, out);
+  }
+}
 
+// always_inline: f is a constant at every call site, so the launcher is called directly, as a hand-written
+// unpacking would
+template <typename R, typename... A, size_t... I>
+__attribute__((always_inline)) inline PyObject* unpack_and_call(R (*f)(A...), const char* name, PyObject* const* a,
+                                                                Py_ssize_t n, std::index_sequence<I...>) {
+  if (n != static_cast<Py_ssize_t>(sizeof...(A))) return bad_nargs(name, sizeof...(A), n);
+  std::tuple<A...> v;
+  if (!(arg_as(a[I], &std::get<I>(v)) && ...)) return nullptr;  // left to right, stops at the first bad argument
+  return PyLong_FromLongLong(static_cast<long long>(f(std::get<I>(v)...)));
+}
+
+// the METH_FASTCALL entry point of launcher F; Name is its Python-visible name (for the argument-count message)
+template <auto F, const char* Name> struct Entry;
+template <typename R, typename... A, R (*F)(A...), const char* Name> struct Entry<F, Name> {
+  static PyObject* call(PyObject*, PyObject* const* a, Py_ssize_t n) {
+    return unpack_and_call(F, Name, a, n, std::index_sequence_for<A...>{});
+  }
+};
+
+// dispatch_gen.inc is a list of PA_ENTRY(name, code) rows. First pass: the table's code against the declaration.
+#define PA_ENTRY(name, code)                                                                  \
+  static_assert(pa_sig::sig(&name) == code, "ops/_sigs.py disagrees with pa_api.h: " #name);  \
+  constexpr char kName_##name[] = #name;
 #include "dispatch_gen.inc"
+#undef PA_ENTRY
 
-namespace {
+// Second pass: the method table.
+#define PA_ENTRY(name, code)                                                                                     \
+  {kName_##name,                                                                                                 \
+   reinterpret_cast<PyCFunction>(reinterpret_cast<void (*)(void)>(Entry<&name, kName_##name>::call)), METH_FASTCALL, \
+   nullptr},
+PyMethodDef kGenMethods[] = {
+#include "dispatch_gen.inc"
+};
+#undef PA_ENTRY
 
 PyObject* set_stream_sentinel(PyObject*, PyObject* o) {
   Py_XDECREF(g_cur_stream);

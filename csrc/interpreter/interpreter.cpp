@@ -15,30 +15,14 @@
 #include <c10/hip/HIPStream.h>
 #include <hip/hip_runtime_api.h>
 
+#include "pa_api.h"  // hand-written kernels (csrc/kernels/*.hip, exported by _C_hip.so)
+
 #include <stdexcept>
 #include <string>
 #include <unordered_map>
 #include <vector>
 
 namespace py = pybind11;
-
-// hand-written kernels (csrc/kernels/*.hip, exported by _C_hip.so)
-extern "C" {
-int pa_gemm_bf16(const void* a, const void* b, void* c, const void* bias, void* aux, int64_t M, int64_t N, int64_t K,
-                 int64_t lda, int64_t ldb, int64_t ldc, int a_kmajor, int b_kmajor, int flags, float alpha, int bn,
-                 int splits, hipStream_t st);
-int pa_gemm_bf16_pp(const void* a, const void* b, void* c, const void* bias, void* aux, int64_t M, int64_t N,
-                    int64_t K, int64_t lda, int64_t ldb, int64_t ldc, int a_kmajor, int b_kmajor, int flags,
-                    float alpha, void* ws, hipStream_t st);
-int64_t pa_gemm_pp_ws_bytes(int64_t M, int64_t N, int64_t K);
-int pa_layer_norm_fwd(const void* x, const void* w, const void* b, void* y, float* mean, float* rstd, int64_t rows,
-                      int64_t cols, float eps, int dtype, hipStream_t st);
-int pa_rms_norm_fwd(const void* x, const void* w, void* y, float* rstd, int64_t rows, int64_t cols, float eps,
-                    int dtype, hipStream_t st);
-int pa_softmax_fwd(const void* x, void* y, int64_t rows, int64_t cols, int dtype, hipStream_t st);
-int pa_flash_attn_fwd(const void* q, const void* k, const void* v, void* o, float* lse, const int64_t* strides, int B,
-                      int Sq, int Sk, int H, int Hk, int D, float scale, int causal, hipStream_t st);
-}
 
 namespace {
 

@@ -27,6 +27,8 @@
 #include <c10/hip/HIPGuard.h>
 #include <hip/hip_runtime_api.h>
 
+#include "pa_api.h"  // hand-written kernels (csrc/kernels/*.hip, exported by _C_hip.so)
+
 #include <cmath>
 #include <cstring>
 #include <stdexcept>
@@ -37,70 +39,6 @@
 namespace py = pybind11;
 using torch::autograd::AutogradContext;
 using torch::autograd::variable_list;
-
-extern "C" {
-struct PaAttnExtra {  // mirror of csrc/kernels/flash_attn.hip
-  const int* cu_q;
-  const int* cu_k;
-  const void* mask;
-  int64_t mask_kind;
-  int64_t ms[3];
-  const int* fm;
-  int64_t fm_cols;
-  int64_t fms[2];
-  const int* fm_stats;
-  int64_t fmst[2];
-  double drop_p;
-  uint64_t seed;
-  int64_t lse_s[2];
-  int64_t dtype;
-};
-int pa_gemm_bf16(const void* a, const void* b, void* c, const void* bias, void* aux, int64_t M, int64_t N, int64_t K,
-                 int64_t lda, int64_t ldb, int64_t ldc, int a_kmajor, int b_kmajor, int flags, float alpha, int bn,
-                 int splits, hipStream_t st);
-int pa_gemm_bf16_pp(const void* a, const void* b, void* c, const void* bias, void* aux, int64_t M, int64_t N,
-                    int64_t K, int64_t lda, int64_t ldb, int64_t ldc, int a_kmajor, int b_kmajor, int flags,
-                    float alpha, void* ws, hipStream_t st);
-int64_t pa_gemm_pp_ws_bytes(int64_t M, int64_t N, int64_t K);
-int pa_layer_norm_fwd(const void* x, const void* w, const void* b, void* y, float* mean, float* rstd, int64_t rows,
-                      int64_t cols, float eps, int dtype, hipStream_t st);
-int pa_layer_norm_bwd(const void* dy, const void* x, const void* w, const float* mean, const float* rstd, void* dx,
-                      float* dw_part, float* db_part, void* res, int64_t rows, int64_t cols, int dtype_np,
-                      hipStream_t st);
-int pa_rms_norm_fwd(const void* x, const void* w, void* y, float* rstd, int64_t rows, int64_t cols, float eps,
-                    int dtype, hipStream_t st);
-int pa_rms_norm_bwd(const void* dy, const void* x, const void* w, const float* rstd, void* dx, float* dw_part,
-                    int64_t rows, int64_t cols, int dtype_np, hipStream_t st);
-int pa_flash_attn_fwd_ex(const void* q, const void* k, const void* v, void* o, float* lse, const int64_t* strides,
-                         int B, int Sq, int Sk, int H, int Hk, int D, float scale, int causal, const PaAttnExtra* ex,
-                         hipStream_t st);
-int pa_flash_attn_bwd_ex(const void* q, const void* k, const void* v, const void* o, const void* dout,
-                         const float* lse, void* dq, void* dk, void* dv, float* dq_acc, float* delta,
-                         const int64_t* strides, int B, int Sq, int Sk, int H, int Hk, int D, float scale, int causal,
-                         int64_t q_rows, const PaAttnExtra* ex, hipStream_t st);
-int pa_softmax_ce_fwd(const void* logits, const int64_t* labels, float* loss, float* lse, int64_t rows, int64_t cols,
-                      int64_t ignore_index, int dtype, hipStream_t st);
-int pa_softmax_ce_bwd(const void* logits, const int64_t* labels, const float* lse, const float* dloss, void* dlogits,
-                      int64_t rows, int64_t cols, int64_t ignore_index, int dtype, hipStream_t st);
-int pa_conv2d_nhwc_fwd(const void* x, const void* w, const void* bias, void* out, const void* zero, int N, int H,
-                       int W, int C, int Cout, int KH, int KW, int stride, int pad_h, int pad_w, int dil, int Ho,
-                       int Wo, hipStream_t st);
-int pa_conv2d_nhwc_wgrad(const void* x, const void* dy, float* ws, const void* zero, int N, int H, int W, int C,
-                         int Cout, int KH, int KW, int stride, int pad_h, int pad_w, int dil, int Ho, int Wo,
-                         int splits, int bn, hipStream_t st);
-int pa_bn_chunks(int64_t R, int C);
-int pa_bn_fwd_nhwc(const void* x, const void* res, void* y, const float* w, const float* b, float* run_mean,
-                   float* run_var, float* save_mean, float* save_rstd, float* partial, float* ss, int64_t R, int C,
-                   float momentum, float eps, int relu, int training, hipStream_t st);
-int pa_bn_bwd_nhwc(const void* dy, const void* x, const void* y, void* dx, void* dres, const float* w,
-                   const float* mean, const float* rstd, float* dw, float* db, float* partial, float* coef, int64_t R,
-                   int C, int relu, int global_stats, const float* ss, hipStream_t st);
-int pa_adamw_multi(const int64_t* table, const int64_t* items, int64_t n_items, const float* inv_scale, float lr,
-                   float b1, float b2, float eps, float wd_unused, float bc1, float bc2, const float* hyper,
-                   hipStream_t st);
-int pa_momentum_multi(const int64_t* table, const int64_t* items, int64_t n_items, const float* inv_scale, float lr,
-                      float mu, float rescale, int nesterov, hipStream_t st);
-}
 
 namespace {
 

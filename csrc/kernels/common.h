@@ -7,7 +7,7 @@
 #include <hip/hip_fp16.h>
 #include <stdint.h>
 
-#define PA_EXPORT extern "C" __attribute__((visibility("default")))
+#include "pa_api.h"  // PA_EXPORT and the declaration every launcher definition is checked against
 
 namespace pa {
 

@@ -16,17 +16,7 @@ static int fa_group(int BH, int nb, int inflight) {
   return std::max(1, (inflight + nb - 1) / nb);
 }
 
-// Optional arguments (mirrors paddlepaddle_amd/ops/attention.py:_AttnExtra, all 8-byte fields).
-struct PaAttnExtra {
-  const int* cu_q; const int* cu_k;
-  const void* mask; int64_t mask_kind; int64_t ms[3];
-  const int* fm; int64_t fm_cols; int64_t fms[2];
-  const int* fm_stats; int64_t fmst[2];
-  double drop_p; uint64_t seed;
-  int64_t lse_s[2];  // 0, 0 -> dense [B, H, Sq]
-  int64_t dtype;     // 0 bf16, 1 fp16
-};
-
+// Optional arguments: PaAttnExtra (pa_api.h).
 template <typename A>
 static void fill_extra(A& a, const PaAttnExtra* ex, int B, int Sq, int H) {
   a.cu_q = nullptr; a.cu_k = nullptr; a.mask = nullptr; a.mask_kind = 0; a.fm = nullptr; a.fm_cols = 0;

@@ -1,8 +1,10 @@
-"""Signature table of every exported launcher in _C_hip.so (see csrc/kernels/*.hip).
+"""The ctypes view of csrc/kernels/pa_api.h, the C API of every exported launcher in _C_hip.so.
 
-Single source of truth for both launch paths: ``_loader`` sets the ctypes argtypes from it, and
-``tools/build_native.py`` generates the native METH_FASTCALL entry points of ``_C_dispatch`` from it
-(csrc/dispatch/dispatch_gen.inc). Pure ctypes, no package imports, so the build can load it by path.
+``_loader`` sets the ctypes argtypes from it (the fallback launch path). The declarations in pa_api.h are the
+source of truth: ``tools/build_native.py`` turns each row into a signature code (csrc/dispatch/dispatch_gen.inc)
+and the build of ``_C_dispatch`` static_asserts it against the header, so a row with the wrong arity, a wrong
+argument kind, a wrong ``RET_I64`` membership or no declaration fails the build. Pure ctypes, no package imports,
+so the build can load it by path.
 """
 import ctypes
 
@@ -40,7 +42,6 @@ SIGS = {
     "pa_adamw_multi": [_vp, _vp, _i64, _vp, _f32, _f32, _f32, _f32, _f32, _f32, _f32, _vp, _vp],
     "pa_adam_hyper_step": [_vp, _f32, _f32, _vp],
     "pa_sq_norm_multi": [_vp, _vp, _i64, _vp, _vp],
-    "pa_scale_multi": [_vp, _i64, _vp, _vp],
     "pa_write_i64": [_vp, _vp, _i64, _vp],
     "pa_bn_set_target_wgs": [_i32],
     "pa_momentum_multi": [_vp, _vp, _i64, _vp, _f32, _f32, _f32, _i32, _vp],
@@ -49,6 +50,7 @@ SIGS = {
     # loss scaling (csrc/kernels/amp.hip)
     "pa_amp_check_unscale_multi": [_vp, _vp, _i64, _vp, _vp, _vp],
     # attention
+    "pa_flash_attn_set_fwd_variant": [_i32],
     "pa_flash_attn_fwd": [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _f32, _i32, _vp],
     "pa_flash_attn_bwd": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                           _i32, _i32, _i32, _i32, _i32, _i32, _f32, _i32, _vp],

@@ -95,7 +95,7 @@ def _i64arr(vals):
 
 
 class _AttnExtra(ctypes.Structure):
-    """Mirror of PaAttnExtra (csrc/kernels/flash_attn.hip): the optional terms of a launch."""
+    """Mirror of PaAttnExtra (csrc/kernels/pa_api.h): the optional terms of a launch."""
     _fields_ = [("cu_q", ctypes.c_void_p), ("cu_k", ctypes.c_void_p), ("mask", ctypes.c_void_p),
                 ("mask_kind", ctypes.c_int64), ("ms", ctypes.c_int64 * 3), ("fm", ctypes.c_void_p),
                 ("fm_cols", ctypes.c_int64), ("fms", ctypes.c_int64 * 2), ("fm_stats", ctypes.c_void_p),

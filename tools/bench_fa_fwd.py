@@ -1,6 +1,5 @@
 """Flash attention forward: kernel variant 1 (register-staged) vs 2 (glds, 2 LDS stages, deferred
 rescale). Checks v2 against v1 and prints TF/s (CUDA events, 20 iterations)."""
-import ctypes
 import os
 import sys
 
@@ -10,7 +9,6 @@ from paddlepaddle_amd.ops import _loader as L  # noqa: E402
 from paddlepaddle_amd.ops.attention import _FlashAttnQKVPackedHIP  # noqa: E402
 
 lib = L.lib()
-lib.pa_flash_attn_set_fwd_variant.argtypes = [ctypes.c_int]
 
 
 def timed(fn, it=20):

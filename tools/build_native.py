@@ -4,10 +4,14 @@
 * ``paddlepaddle_amd/_C_hip.so``     — every csrc/kernels/*.hip, hipcc --offload-arch=gfx950, C ABI
                                         (loaded with ctypes by paddlepaddle_amd.ops._loader)
 * ``paddlepaddle_amd/_C_runtime*.so`` — csrc/runtime/*.cpp, g++ + pybind11 (CPU runtime)
-* ``paddlepaddle_amd/_C_dispatch*.so`` — csrc/dispatch/dispatch.cpp + generated entry points: the native
-                                        launch path of every ``pa_*`` launcher (links _C_hip.so, libtorch)
+* ``paddlepaddle_amd/_C_dispatch*.so`` — csrc/dispatch/dispatch.cpp: the native launch path of every ``pa_*``
+                                        launcher, one template instantiation per declaration in
+                                        csrc/kernels/pa_api.h (links _C_hip.so, libtorch). dispatch_gen.inc, generated
+                                        from the ctypes table ops/_sigs.py, is the list of launchers and the check
+                                        that the table agrees with pa_api.h: a disagreement fails this build.
 
-Incremental: an object is rebuilt only when its source or common.h is newer. Parallel compile.
+Incremental: an object is rebuilt only when its source or a header of csrc/kernels is newer; the C++ callers of the
+kernels also when pa_api.h is. Parallel compile.
 """
 from __future__ import annotations
 
@@ -23,6 +27,8 @@ ROCM = os.environ.get("ROCM_PATH", "/opt/rocm")
 ARCH = os.environ.get("PYTORCH_ROCM_ARCH", "gfx950")
 BUILD = os.path.join(ROOT, "build", "native")
 PKG = os.path.join(ROOT, "paddlepaddle_amd")
+KERNELS = os.path.join(ROOT, "csrc", "kernels")
+PA_API = os.path.join(KERNELS, "pa_api.h")  # the C API of _C_hip.so, included by every C++ caller of the kernels
 
 HIP_FLAGS = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-munsafe-fp-atomics",
              "-Wno-unused-result", "-Wno-unused-variable"]
@@ -97,48 +103,40 @@ def build_alloc(verbose=False):
     return out
 
 
-_CTYPE_TO_C = {"c_void_p": ("void*", "ptr"), "c_long": ("int64_t", "i64"), "c_longlong": ("int64_t", "i64"),
-               "c_int": ("int", "i32"), "c_float": ("float", "f32"), "c_ulong": ("uint64_t", "u64"),
-               "c_ulonglong": ("uint64_t", "u64")}
+_CTYPE_TO_CODE = {"c_void_p": "p", "c_long": "l", "c_longlong": "l", "c_int": "i", "c_float": "f", "c_ulong": "u",
+                  "c_ulonglong": "u"}
 
 
-def gen_dispatch():
-    """csrc/dispatch/dispatch_gen.inc: one METH_FASTCALL entry point per launcher in ops/_sigs.py."""
+def _load_sigs():
     import importlib.util
     spec = importlib.util.spec_from_file_location("_pa_sigs", os.path.join(PKG, "ops", "_sigs.py"))
     m = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(m)
-    nm = subprocess.run(["nm", "-D", "--defined-only", os.path.join(PKG, "_C_hip.so")], capture_output=True,
-                        text=True, check=True).stdout
-    exported = {ln.split()[-1] for ln in nm.splitlines() if ln.strip()}
-    out = ["// generated by tools/build_native.py from paddlepaddle_amd/ops/_sigs.py -- do not edit", ""]
-    names = []
+    return m
+
+
+def dispatch_gen_text():
+    """The text of csrc/dispatch/dispatch_gen.inc: one ``PA_ENTRY(name, code)`` row per launcher in ops/_sigs.py,
+    the code being the return type's letter then one per argument (csrc/dispatch/sig_code.h). dispatch.cpp
+    static_asserts each code against the declaration in csrc/kernels/pa_api.h, so a row that is wrong, or that has
+    no declaration, stops the build."""
+    m = _load_sigs()
+    out = ["// generated by tools/build_native.py from paddlepaddle_amd/ops/_sigs.py -- do not edit"]
     for name, args in m.SIGS.items():
-        if name not in exported:
-            continue  # declared for an optional launcher this build does not export
-        ctys = [_CTYPE_TO_C[a.__name__] for a in args]
-        ret = "int64_t" if name in m.RET_I64 else "int"
-        out.append(f'extern "C" {ret} {name}({", ".join(c for c, _ in ctys)});')
-        out.append(f"static PyObject* w_{name}(PyObject*, PyObject* const* a, Py_ssize_t n) {{")
-        out.append(f'  if (n != {len(ctys)}) return bad_nargs("{name}", {len(ctys)}, n);')
-        for i, (c, k) in enumerate(ctys):
-            out.append(f"  {c} a{i};")
-            out.append(f"  if (!arg_{k}(a[{i}], &a{i})) return nullptr;")
-        call = f"{name}({', '.join(f'a{i}' for i in range(len(ctys)))})"
-        out.append(f"  return PyLong_FromLongLong(static_cast<long long>({call}));")
-        out.append("}")
-        names.append(name)
-    out.append("static PyMethodDef kGenMethods[] = {")
-    for name in names:
-        out.append(f'    {{"{name}", reinterpret_cast<PyCFunction>(reinterpret_cast<void (*)(void)>(w_{name})), '
-                   f"METH_FASTCALL, nullptr}},")
-    out.append("};")
-    text = "\n".join(out) + "\n"
-    path = os.path.join(ROOT, "csrc", "dispatch", "dispatch_gen.inc")
-    if not os.path.exists(path) or open(path).read() != text:
-        with open(path, "w") as f:
+        code = ("l" if name in m.RET_I64 else "i") + "".join(_CTYPE_TO_CODE[a.__name__] for a in args)
+        out.append(f'PA_ENTRY({name}, "{code}")')
+    return "\n".join(out) + "\n"
+
+
+DISPATCH_GEN = os.path.join(ROOT, "csrc", "dispatch", "dispatch_gen.inc")
+
+
+def gen_dispatch():
+    text = dispatch_gen_text()
+    if not os.path.exists(DISPATCH_GEN) or open(DISPATCH_GEN).read() != text:
+        with open(DISPATCH_GEN, "w") as f:
             f.write(text)
-    return path
+    return DISPATCH_GEN
 
 
 def build_dispatch(verbose=False):
@@ -148,9 +146,10 @@ def build_dispatch(verbose=False):
     suffix = sysconfig.get_config_var("EXT_SUFFIX") or ".so"
     out = os.path.join(PKG, "_C_dispatch" + suffix)
     hip_so = os.path.join(PKG, "_C_hip.so")
-    if not _newer([src, gen, hip_so], out):
+    if not _newer([src, gen, os.path.join(ROOT, "csrc", "dispatch", "sig_code.h"), PA_API, hip_so], out):
         return out
-    inc = [f"-I{d}" for d in ce.include_paths()] + [f"-I{sysconfig.get_paths()['include']}", f"-I{ROCM}/include"]
+    inc = [f"-I{d}" for d in ce.include_paths()] + [f"-I{sysconfig.get_paths()['include']}", f"-I{ROCM}/include",
+                                                     f"-I{KERNELS}"]
     libs = [f"-L{d}" for d in ce.library_paths()] + [ "-ltorch_python", "-ltorch", "-ltorch_cpu", "-lc10", "-lc10_hip",
             f"-L{PKG}", "-l:_C_hip.so", f"-L{ROCM}/lib", "-lamdhip64", "-Wl,-rpath,$ORIGIN"]
     _run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-D__HIP_PLATFORM_AMD__=1", "-DUSE_ROCM=1",
@@ -168,9 +167,10 @@ def build_interp(verbose=False):
     suffix = sysconfig.get_config_var("EXT_SUFFIX") or ".so"
     out = os.path.join(PKG, "_C_interp" + suffix)
     hip_so = os.path.join(PKG, "_C_hip.so")
-    if not _newer([src, hip_so], out):
+    if not _newer([src, PA_API, hip_so], out):
         return out
-    inc = [f"-I{d}" for d in ce.include_paths()] + [f"-I{sysconfig.get_paths()['include']}", f"-I{ROCM}/include"]
+    inc = [f"-I{d}" for d in ce.include_paths()] + [f"-I{sysconfig.get_paths()['include']}", f"-I{ROCM}/include",
+                                                     f"-I{KERNELS}"]
     # links the hand-written kernels (_C_hip.so) and c10_hip (current HIP stream), like _C_dispatch
     libs = [f"-L{d}" for d in ce.library_paths()] + ["-ltorch_python", "-ltorch", "-ltorch_cpu", "-lc10", "-lc10_hip",
                                                       f"-L{PKG}", "-l:_C_hip.so", f"-L{ROCM}/lib", "-lamdhip64",
@@ -191,9 +191,10 @@ def build_train(verbose=False):
     suffix = sysconfig.get_config_var("EXT_SUFFIX") or ".so"
     out = os.path.join(PKG, "_C_train" + suffix)
     hip_so = os.path.join(PKG, "_C_hip.so")
-    if not _newer([src, hip_so], out):
+    if not _newer([src, PA_API, hip_so], out):
         return out
-    inc = [f"-I{d}" for d in ce.include_paths()] + [f"-I{sysconfig.get_paths()['include']}", f"-I{ROCM}/include"]
+    inc = [f"-I{d}" for d in ce.include_paths()] + [f"-I{sysconfig.get_paths()['include']}", f"-I{ROCM}/include",
+                                                     f"-I{KERNELS}"]
     libs = [f"-L{d}" for d in ce.library_paths()] + ["-ltorch_python", "-ltorch", "-ltorch_cpu", "-lc10", "-lc10_hip",
                                                       f"-L{PKG}", "-l:_C_hip.so", f"-L{ROCM}/lib", "-lamdhip64",
                                                       "-Wl,-rpath,$ORIGIN"]
