@@ -452,7 +452,8 @@ def _lse_reference(q, k, causal, scale, mask):
         s = s.masked_fill(~torch.ones(Sq, Sk, dtype=torch.bool, device=q.device).tril(Sk - Sq), float("-inf"))
     if mask is not None:
         s = s.masked_fill(~mask, float("-inf")) if mask.dtype == torch.bool else s + mask.float()
-    return torch.logsumexp(s, -1)
+    lse = torch.logsumexp(s, -1)
+    return lse.masked_fill(torch.isneginf(lse), float("inf"))  # no visible key: +inf, the kernel's value
 
 
 def flashmask_keep(startend, Sq, Sk, causal, device):
@@ -493,15 +494,27 @@ def paged_decode_reference(q, key_cache, value_cache, block_tables, lens, scale=
     scale = 1.0 / math.sqrt(D) if scale is None else float(scale)
     nblk = block_tables.shape[1]
     tab = block_tables.long()
-    K = key_cache[tab].permute(0, 2, 1, 3, 4).reshape(N, Hkv, nblk * bs, D).float()
-    V = value_cache[tab].permute(0, 2, 1, 3, 4).reshape(N, Hkv, nblk * bs, D).float()
-    G = H // Hkv
-    qf = q.float().view(N, Hkv, G, D)
-    s = torch.einsum("nkgd,nkld->nkgl", qf, K) * scale
+    K = key_cache[tab].permute(0, 2, 1, 3, 4).reshape(N, Hkv, nblk * bs, D)
+    V = value_cache[tab].permute(0, 2, 1, 3, 4).reshape(N, Hkv, nblk * bs, D)
     valid = torch.arange(nblk * bs, device=q.device)[None] < lens.long()[:, None]
+    return _decode_math(q, K, V, valid, scale)
+
+
+def _decode_math(q, K, V, valid, scale):
+    """softmax(q K^T * scale) V over the valid keys only: q [N, H, D]; K, V [N, Hkv, L, D]; valid bool [N, L]. Slots
+    past a sequence's length never reach the result, whatever they hold (a cache from torch.empty may hold NaN /
+    Inf, and 0 * NaN = NaN), and a sequence without a valid key gives zeros: both as the HIP kernel, which never
+    reads those slots."""
+    N, H, D = q.shape
+    Hkv = K.shape[1]
+    keep = valid[:, None, :, None]
+    K = torch.where(keep, K.float(), torch.zeros((), device=q.device))
+    V = torch.where(keep, V.float(), torch.zeros((), device=q.device))
+    s = torch.einsum("nkgd,nkld->nkgl", q.float().view(N, Hkv, H // Hkv, D), K) * scale
     s = s.masked_fill(~valid[:, None, None], float("-inf"))
-    o = torch.einsum("nkgl,nkld->nkgd", torch.softmax(s, -1), V)
-    return o.reshape(N, H, D).to(q.dtype)
+    empty = ~valid.any(-1)[:, None, None, None]
+    p = torch.softmax(s.masked_fill(empty, 0.0), -1).masked_fill(empty, 0.0)
+    return torch.einsum("nkgl,nkld->nkgd", p, V).reshape(N, H, D).to(q.dtype)
 
 
 def _decode_splits(N, Hkv, max_len, bs):
@@ -576,11 +589,7 @@ def dense_decode_attention(q, key_cache, value_cache, lens, scale=None, max_len=
     scale = 1.0 / math.sqrt(D) if scale is None else float(scale)
     if not _decode_hip_ok(q, key_cache, value_cache, Hkv) or Lc % _VBLK != 0:
         valid = torch.arange(Lc, device=q.device)[None] < lens.long()[:, None]
-        G = H // Hkv
-        s = torch.einsum("nkgd,nkld->nkgl", q.float().view(N, Hkv, G, D), key_cache.float()) * scale
-        s = s.masked_fill(~valid[:, None, None], float("-inf"))
-        o = torch.einsum("nkgl,nkld->nkgd", torch.softmax(s, -1), value_cache.float())
-        return o.reshape(N, H, D).to(q.dtype)
+        return _decode_math(q, key_cache, value_cache, valid, scale)
     nb = Lc // _VBLK
     key = (N, Hkv, nb, q.device)
     tables = _DENSE_TABLES.get(key)
