@@ -54,6 +54,16 @@ __device__ __forceinline__ float lo_f16(uint32_t w) {
 __device__ __forceinline__ float hi_f16(uint32_t w) {
   uint16_t u = (uint16_t)(w >> 16); return __half2float(*reinterpret_cast<f16*>(&u));
 }
+// four consecutive 16-bit values (bf16, or fp16 with F16) in one 8-byte read: the bias quad of the GEMM epilogues
+template <bool F16 = false>
+__device__ __forceinline__ void load4_16(const uint16_t* p, float* f) {
+  const uint2 w = *reinterpret_cast<const uint2*>(p);
+  if (F16) {
+    f[0] = lo_f16(w.x); f[1] = hi_f16(w.x); f[2] = lo_f16(w.y); f[3] = hi_f16(w.y);
+  } else {
+    f[0] = lo_bf16(w.x); f[1] = hi_bf16(w.x); f[2] = lo_bf16(w.y); f[3] = hi_bf16(w.y);
+  }
+}
 
 // ---- 8-element vector load/store into float[8] (16-bit types: one 16-byte access; fp32: two)
 template <typename T> __device__ __forceinline__ void load8(const T* p, float* f);

@@ -17,8 +17,10 @@
 //     v_mfma_f32_16x16x32_bf16, operands swapped (D = B^T-frag x A-frag) so each lane ends with
 //     4 consecutive output columns of one row -> 8/16-byte epilogue stores.
 //   * the LDS tile primitives (glds16 LDS-DMA, lds_tr, bar, vm_wait, the swizzles, stage<R, KMAJ, NW>,
-//     frag<R, KMAJ>, xcd_remap, tile_coords) are the shared ones of mfma_tile.h; this file keeps what is its
-//     own: the K-loops and schedules, Loader32 / frag32, the conv gathers and the epilogues.
+//     frag<R, KMAJ>, xcd_remap, tile_coords) are the shared ones of mfma_tile.h, and the 256x256 ping-pong
+//     schedule (main loop, tail-slice decode, partial store, one-pass 16-bit epilogue) is pingpong256.h, shared
+//     with gemm_fp8.hip; this file keeps what is its own: the other K-loops and schedules, Loader32 / frag32,
+//     the conv gathers and the remaining epilogues.
 //   * global -> LDS by LDS-DMA (glds16, no VGPR staging), two LDS stages (128 KiB for
 //     256x256): tile t+1 is in flight while tile t is consumed.
 //   * K-major images: [rows][64 k] with 128-B rows, 16-B chunk XOR-swizzle chunk ^ k_swz(row):
@@ -33,6 +35,7 @@
 #include "gemm_plan.h"
 #include "launch.h"
 #include "mfma_tile.h"
+#include "pingpong256.h"
 
 #include <type_traits>
 
@@ -337,10 +340,7 @@ __global__ __launch_bounds__(NW * 64, 1) void gemm_bf16_kernel(GemmArgs p0) {
     float bsc[4] = {0.f, 0.f, 0.f, 0.f}, bsh[4] = {0.f, 0.f, 0.f, 0.f}, bmu[4] = {0.f, 0.f, 0.f, 0.f};
     if (flags & kEpiStatsBwd) bn_cols(p, n, bsc, bsh, bmu);
     float bv[4] = {0.f, 0.f, 0.f, 0.f};
-    if (flags & kEpiBias) {
-      const uint2 braw = *reinterpret_cast<const uint2*>(p.bias + n);
-      bv[0] = lo_bf16(braw.x); bv[1] = hi_bf16(braw.x); bv[2] = lo_bf16(braw.y); bv[3] = hi_bf16(braw.y);
-    }
+    if (flags & kEpiBias) load4_16(p.bias + n, bv);
 #pragma unroll
     for (int i = 0; i < MR; ++i) {
       const int m = mrow0 + i * 16;
@@ -385,24 +385,12 @@ __global__ __launch_bounds__(NW * 64, 1) void gemm_bf16_kernel(GemmArgs p0) {
 
 // ---------------------------------------------------------------------------------------------
 // 256x256x64 8-wave kernel with the 4-phase-per-K-tile interleave (cdna_hip_programming.md 5,
-// "256^2 8-phase template"): every K-tile is split into four 16-KiB half-tiles
-//   H0 = A rows 0..127, H1 = B cols 0..127, H2 = A rows 128..255, H3 = B cols 128..255
-// and each phase {ds_read a register subtile ; issue ONE half-tile of glds ; barrier ; 16 MFMA ;
-// barrier}. Reads: phase 0 H0+H1, phase 1 H3, phase 2 H2. Half-tile j (= 4 * tile + h) is issued in
-// phase j - 6, so 5-6 phases of load latency are hidden, and each read is preceded by a counted vmcnt
-// in the phase before it. The wm == 1 waves run one barrier behind the wm == 0 waves (ping-pong:
-// per SIMD one wave is in its MFMA cluster while the other reads LDS / issues glds); because of the
-// stagger a half-tile is restaged at least two phases after its last ds_read (WAR), and a read
-// happens at least one barrier after the wait that retires it in both wave groups (RAW).
-// Wave (wm, wn) owns rows {wm*64.., 128+wm*64..} x cols {wn*32.., 128+wn*32..}: the four phases
-// compute its quadrants (top,L) (top,R) (bottom,L) (bottom,R).
-constexpr int kEpiRowStride = 260;      // fp32 per row of the epilogue image (256 + 4 padding)
-constexpr int kEpiRowStrideBf16 = 264;  // bf16 per row of the one-pass bf16 epilogue image (528-byte rows)
+// "256^2 8-phase template"). The schedule itself (half-tiles, issue distance, counted waits, the barrier
+// stagger of the wm == 1 waves) is PPLoop of pingpong256.h, shared with gemm_fp8.hip; per phase a wave runs
+// 16 v_mfma_f32_16x16x32_bf16. This file supplies the bf16 policy (fragments of K-major or MN-major images, plain
+// or segmented staging) and the fp32 two-half staged epilogue.
+constexpr int kEpiRowStride = 260;  // fp32 per row of the epilogue image (256 + 4 padding)
 
-using H0_ = IntC<0>;
-using H1_ = IntC<1>;
-using H2_ = IntC<2>;
-using H3_ = IntC<3>;
 using True_ = IntC<1>;
 using False_ = IntC<0>;
 
@@ -515,49 +503,29 @@ __device__ __forceinline__ void colsum_finish(const GemmArgs& p, float* red, con
   }
 }
 
+// The bf16 policy of PPLoop: two 16x16x32 k-substeps per K-tile of 64.
 // SEG: 0 plain operands; 1 K-segmented, 2 N-segmented operands (GemmArgs::nseg, pa_gemm_bf16_pp_segs). The
 // segment selection is compiled only into the segmented instantiations: the plain kernel's staging code (and its
 // register allocation) is the unsegmented ping-pong loop.
-template <bool AK, bool BKM, int SEG = 0>
-__global__ __launch_bounds__(kThreads, 1) void gemm256_kernel(GemmArgs p0) {
-  GemmArgs p = split_view<AK, BKM>(p0);
-  constexpr int HALF = 128 * kBK * 2;  // 16 KiB
-  constexpr int STAGE = 4 * HALF;
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-
-  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-  const int wm = wave >> 2, wn = wave & 3;
-
-  // Balanced tail: the first full_tiles workgroups (a whole number of waves over the CUs) own whole
-  // tiles; the remaining tiles are cut along K so the last wave is as wide as the chip (320 tiles of a
-  // 4096 x 5120 output on 256 CUs: 256 whole + 64 x 4 quarter tiles = 1.25 tile-times instead of 2).
-  const int bid = (int)blockIdx.x;
-  int pid;
-  float* tail_out = nullptr;
-  int kt0 = 0;  // first global K-tile of this workgroup (tail slices start inside K)
-  if (p.tail_split > 0 && bid >= p.full_tiles) {
-    const int u = bid - p.full_tiles;
-    const int ks = u % p.tail_split;
-    pid = p.full_tiles + u / p.tail_split;
-    p.K /= p.tail_split;
-    if constexpr (SEG == 0) {  // plain operands: the slice's operand bases move (the round-4 kernel)
-      p.a += (int64_t)ks * p.K * (AK ? 1 : p.lda);
-      p.b += (int64_t)ks * p.K * (BKM ? 1 : p.ldb);
-    } else {  // segmented operands: the slice's first global K-tile selects the segment
-      kt0 = ks * (p.K / kBK);
-    }
-    tail_out = p.tail_ws + (int64_t)u * 65536;
-  } else {
-    pid = xcd_remap(bid, p.tail_split > 0 ? p.full_tiles : p.tiles_m * p.tiles_n);
+template <bool AK, bool BKM, int SEG>
+struct PP256Ops {
+  static constexpr int kSub = 2;
+  using Frag = bf16x8_t;
+  const GemmArgs& p;
+  int m0, n0, wave, lane;
+  int kt0;  // first global K-tile of this workgroup (tail slices of segmented operands start inside K)
+  static __device__ __forceinline__ Frag read_a(const char* img, int rbase, int ks, int lane) {
+    return frag<128, AK>(img, rbase, ks, lane);
   }
-  int tm, tn;
-  tile_coords(pid, p.tiles_m, p.tiles_n, &tm, &tn);
-  const int m0 = tm * 256, n0 = tn * 256;
-  const int nk = p.K / kBK;
-
+  static __device__ __forceinline__ Frag read_b(const char* img, int rbase, int ks, int lane) {
+    return frag<128, BKM>(img, rbase, ks, lane);
+  }
+  static __device__ __forceinline__ f32x4 mma(Frag b, Frag a, f32x4 c) {
+    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(b, a, c, 0, 0, 0);
+  }
   // Staging of the A (h = 0, 2: rows m0, m0 + 128) or B (h = 1, 3: columns n0, n0 + 128) half of local K-tile t,
   // through the operand segments when there are any (wave-uniform selects).
-  auto stage_half = [&](int t, int h, char* dst) {
+  __device__ __forceinline__ void stage_half(int t, int h, char* dst) const {
     const int tg = SEG == 0 ? t : kt0 + t;
     int k0 = tg * kBK;
     const uint16_t* a = p.a;
@@ -585,166 +553,60 @@ __global__ __launch_bounds__(kThreads, 1) void gemm256_kernel(GemmArgs p0) {
       }
       stage<128, BKM>(b, ldb, c0, cmax, k0, dst, wave, lane);
     }
-  };
-  // issue half-tile j (tile j>>2, half j&3) into buffer (j>>2)&1
-  auto issue = [&](int j) {
-    const int t = j >> 2, h = j & 3;
-    stage_half(t, h, smem + (t & 1) * STAGE + h * HALF);
-  };
-  // the same with the half known at compile time (steady-state body: no branch on h)
-  auto issue_h = [&](int t, auto hc) {
-    constexpr int h = decltype(hc)::value;
-    stage_half(t, h, smem + (t & 1) * STAGE + h * HALF);
-  };
+  }
+};
+
+template <bool AK, bool BKM, int SEG = 0>
+__global__ __launch_bounds__(kThreads, 1) void gemm256_kernel(GemmArgs p0) {
+  GemmArgs p = split_view<AK, BKM>(p0);
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const int wm = wave >> 2, wn = wave & 3;
+
+  const PPWork w = pp_work(p, (int)blockIdx.x);
+  int kt0 = 0;
+  if (w.tail_out) {
+    if constexpr (SEG == 0) {  // plain operands: the slice's operand bases move
+      p.a += (int64_t)w.ks * p.K * (AK ? 1 : p.lda);
+      p.b += (int64_t)w.ks * p.K * (BKM ? 1 : p.ldb);
+    } else {  // segmented operands: the slice's first global K-tile selects the segment
+      kt0 = w.ks * (p.K / kBK);
+    }
+  }
+  int tm, tn;
+  tile_coords(w.pid, p.tiles_m, p.tiles_n, &tm, &tn);
+  const int m0 = tm * 256, n0 = tn * 256;
 
   f32x4 acc[2][4][2][2];
-#pragma unroll
-  for (int a = 0; a < 2; ++a)
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-      for (int b = 0; b < 2; ++b)
-#pragma unroll
-        for (int j = 0; j < 2; ++j) acc[a][i][b][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-  // Half-tile j is issued in phase j - 6 (phase = 4 * tile + p). Before each phase that reads a
-  // half-tile the waves wait (in the previous phase, before its first barrier) until that half-tile
-  // is retired: vmcnt = 2 * (half-tiles issued after it).
-  const int last_j = 4 * nk - 1;
-  auto wait_for = [&](int phase, int jstar) {
-    const int issued = min(phase + 6, last_j);
-    vm_wait(2 * max(issued - jstar, 0));
-  };
-  const int npro = min(6, 4 * nk);
+  const PP256Ops<AK, BKM, SEG> ops{p, m0, n0, wave, lane, kt0};
+  const int nk = p.K / kBK;
+  PPLoop<PP256Ops<AK, BKM, SEG>> L{ops, smem, nk, wm, wn, lane, acc};
+  L.start();
+  int t = 0;  // the two K loops stay in the kernel: see PPLoop
 #pragma unroll 1
-  for (int j = 0; j < npro; ++j) issue(j);
-  vm_wait(2 * max(min(5, last_j) - 1, 0));  // H0, H1 of tile 0
-  bar();
-  // ping-pong: the wm == 1 waves run one barrier behind, so on every SIMD one wave issues its
-  // MFMA cluster while the other does its ds_reads / glds (+1 barrier at the end for wm == 0).
-  const bool lag = __builtin_amdgcn_readfirstlane(wm) == 1;
-  if (lag) bar();
-
-  bf16x8_t af[4][2], bl[2][2], br[2][2];
-  const int ar = wm * 64, bc = wn * 32;
-
-  // One K-tile = 4 phases. STEADY (t <= nk - 3): every issue happens and every wait count is the
-  // constant of the formula above (issued - jstar = 3, 5, 4 half-tiles -> vmcnt 6, 10, 8), so the body
-  // has no branches; the last two tiles run the generic body with clamped counts.
-  auto ktile = [&](int t, auto steady) {
-    constexpr bool S = decltype(steady)::value;
-    const char* buf = smem + (t & 1) * STAGE;
-    const int ph = 4 * t;
-    // ---- phase 0: read A-top + B-left; issue j = ph + 6; MFMA (top, L)
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks)
-#pragma unroll
-      for (int j = 0; j < 2; ++j) bl[j][ks] = frag<128, BKM>(buf + HALF, bc + j * 16, ks, lane);
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks)
-#pragma unroll
-      for (int i = 0; i < 4; ++i) af[i][ks] = frag<128, AK>(buf, ar + i * 16, ks, lane);
-    if (S) {
-      issue_h(t + 1, H2_{});
-      asm volatile("s_waitcnt vmcnt(6)" ::: "memory");  // B-right of this tile, read in phase 1
-    } else {
-      if (ph + 6 <= last_j) issue(ph + 6);
-      wait_for(ph, ph + 3);
-    }
-    bar();
-    __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks)
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-          acc[0][i][0][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bl[j][ks], af[i][ks], acc[0][i][0][j], 0, 0, 0);
-    __builtin_amdgcn_s_setprio(0);
-    bar();
-    // ---- phase 1: read B-right; issue j = ph + 7; MFMA (top, R)
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks)
-#pragma unroll
-      for (int j = 0; j < 2; ++j) br[j][ks] = frag<128, BKM>(buf + 3 * HALF, bc + j * 16, ks, lane);
-    if (S) {
-      issue_h(t + 1, H3_{});
-      asm volatile("s_waitcnt vmcnt(10)" ::: "memory");  // A-bottom of this tile, read in phase 2
-    } else {
-      if (ph + 7 <= last_j) issue(ph + 7);
-      wait_for(ph + 1, ph + 2);
-    }
-    bar();
-    __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks)
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-          acc[0][i][1][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(br[j][ks], af[i][ks], acc[0][i][1][j], 0, 0, 0);
-    __builtin_amdgcn_s_setprio(0);
-    bar();
-    // ---- phase 2: read A-bottom; issue j = ph + 8; MFMA (bottom, L)
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks)
-#pragma unroll
-      for (int i = 0; i < 4; ++i) af[i][ks] = frag<128, AK>(buf + 2 * HALF, ar + i * 16, ks, lane);
-    if (S) issue_h(t + 2, H0_{});
-    else if (ph + 8 <= last_j) issue(ph + 8);
-    bar();
-    __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks)
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-          acc[1][i][0][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bl[j][ks], af[i][ks], acc[1][i][0][j], 0, 0, 0);
-    __builtin_amdgcn_s_setprio(0);
-    bar();
-    // ---- phase 3: issue j = ph + 9; wait for H0/H1 of tile t+1; MFMA (bottom, R)
-    if (S) {
-      issue_h(t + 2, H1_{});
-      asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-    } else {
-      if (ph + 9 <= last_j) issue(ph + 9);
-      if (t + 1 < nk) wait_for(ph + 3, ph + 5);
-    }
-    bar();
-    __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks)
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-          acc[1][i][1][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(br[j][ks], af[i][ks], acc[1][i][1][j], 0, 0, 0);
-    __builtin_amdgcn_s_setprio(0);
-    bar();
-  };
-  const int nsteady = max(nk - 2, 0);
-  int t = 0;
+  for (; t < L.nsteady(); ++t) L.ktile(t, IntC<1>{});
 #pragma unroll 1
-  for (; t < nsteady; ++t) ktile(t, True_{});
-#pragma unroll 1
-  for (; t < nk; ++t) ktile(t, False_{});
-  if (!lag) bar();
+  for (; t < nk; ++t) L.ktile(t, IntC<0>{});
+  L.finish();
 
-  if (tail_out) {  // K-slice of a tail tile: raw fp32 partial, row-major 256 x 256
-#pragma unroll
-    for (int bh = 0; bh < 2; ++bh)
-#pragma unroll
-      for (int j = 0; j < 2; ++j)
-#pragma unroll
-        for (int ah = 0; ah < 2; ++ah)
-#pragma unroll
-          for (int i = 0; i < 4; ++i) {
-            const int r = ah * 128 + ar + i * 16 + (lane & 15);
-            const int c = bh * 128 + bc + j * 16 + 4 * (lane >> 4);
-            const f32x4 v = acc[ah][i][bh][j];
-            *reinterpret_cast<float4*>(tail_out + r * 256 + c) = make_float4(v[0], v[1], v[2], v[3]);
-          }
+  if (w.tail_out) {
+    pp_store_partial(w.tail_out, acc, wm, wn, lane);
+    return;
+  }
+
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  const int flags = p.flags;
+  if (!(flags & kEpiStaged)) {
+    // bf16 output without aux / accumulate: alpha, bias and GELU applied in registers, the finished bf16 tile
+    // staged through LDS in one pass instead of two fp32 halves
+    pp_epilogue16(
+        smem, acc, reinterpret_cast<uint16_t*>(p.c), p.ldc, p.M, p.N, m0, n0, p.alpha, tid,
+        [&](int n, float* bq) {
+          if ((flags & kEpiBias) && n < p.N) load4_16(p.bias + n, bq);
+        },
+        [&](float v) { return (flags & kEpiGelu) ? gelu_tanh(v) : v; },
+        [](float a, float b) { return pack_bf16(a, b); });
     return;
   }
 
@@ -754,53 +616,7 @@ __global__ __launch_bounds__(kThreads, 1) void gemm256_kernel(GemmArgs p0) {
   // 512-byte (bf16) / 1 KiB (fp32) row segments — bias / alpha / pre-activation / GELU / accumulate are
   // applied in that coalesced phase. The scattered 8-byte fragment stores left the tile wave's final burst
   // (aux / accumulate read-modify-write) far below the HBM rate.
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  const int flags = p.flags;
-  if (!(flags & kEpiStaged)) {
-    // bf16 output without aux / accumulate: alpha, bias and GELU applied in registers, the finished bf16 tile
-    // staged through LDS in one pass ([256][264] bf16, 528-byte rows) instead of two fp32 halves
-    uint16_t* im = reinterpret_cast<uint16_t*>(smem);
-    constexpr int RSB = kEpiRowStrideBf16;
-    bar();
-#pragma unroll
-    for (int bh = 0; bh < 2; ++bh)
-#pragma unroll
-      for (int j = 0; j < 2; ++j) {
-        const int c = bh * 128 + bc + j * 16 + 4 * (lane >> 4);
-        float bq[4] = {0.f, 0.f, 0.f, 0.f};
-        if ((flags & kEpiBias) && n0 + c < p.N) {
-          const uint2 braw = *reinterpret_cast<const uint2*>(p.bias + n0 + c);
-          bq[0] = lo_bf16(braw.x); bq[1] = hi_bf16(braw.x); bq[2] = lo_bf16(braw.y); bq[3] = hi_bf16(braw.y);
-        }
-#pragma unroll
-        for (int ah = 0; ah < 2; ++ah)
-#pragma unroll
-          for (int i = 0; i < 4; ++i) {
-            const int r = ah * 128 + ar + i * 16 + (lane & 15);
-            float v[4];
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-              v[e] = acc[ah][i][bh][j][e] * p.alpha + bq[e];
-              if (flags & kEpiGelu) v[e] = gelu_tanh(v[e]);
-            }
-            *reinterpret_cast<uint2*>(im + r * RSB + c) = make_uint2(pack_bf16(v[0], v[1]), pack_bf16(v[2], v[3]));
-          }
-      }
-    bar();
-    const int ecb = (tid & 31) * 8, erb = tid >> 5;
-    const int nb_ = n0 + ecb;
-    if (nb_ < p.N) {
-#pragma unroll 4
-      for (int step = 0; step < 16; ++step) {
-        const int r = step * 16 + erb;
-        const int m = m0 + r;
-        if (m >= p.M) break;
-        *reinterpret_cast<uint4*>(reinterpret_cast<uint16_t*>(p.c) + (int64_t)m * p.ldc + nb_) =
-            *reinterpret_cast<const uint4*>(im + r * RSB + ecb);
-      }
-    }
-    return;
-  }
+  const int ar = wm * 64, bc = wn * 32;
   float* img = reinterpret_cast<float*>(smem);
   constexpr int RS = kEpiRowStride;  // floats per image row
   float bv[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
@@ -1264,10 +1080,7 @@ __global__ __launch_bounds__(kThreads, 1) void gemm3s_kernel(GemmArgs p0) {
     float bsc[4] = {0.f, 0.f, 0.f, 0.f}, bsh[4] = {0.f, 0.f, 0.f, 0.f}, bmu[4] = {0.f, 0.f, 0.f, 0.f};
     if (flags & kEpiStatsBwd) bn_cols(p, n, bsc, bsh, bmu);
     float bv[4] = {0.f, 0.f, 0.f, 0.f};
-    if (flags & kEpiBias) {
-      const uint2 braw = *reinterpret_cast<const uint2*>(p.bias + n);
-      bv[0] = lo_bf16(braw.x); bv[1] = hi_bf16(braw.x); bv[2] = lo_bf16(braw.y); bv[3] = hi_bf16(braw.y);
-    }
+    if (flags & kEpiBias) load4_16(p.bias + n, bv);
 #pragma unroll
     for (int i = 0; i < MR; ++i) {
       const int m = mrow0 + i * 16;
@@ -1338,9 +1151,8 @@ int launch256_seg(GemmArgs a, int splits, hipStream_t st, int grid) {
     grid = a.tiles_m * a.tiles_n;
     a.tail_split = 0;
   }
-  constexpr int kLoop = 2 * 4 * 128 * kBK * 2, kEpi0 = 128 * kEpiRowStride * 4, kEpi1 = 256 * kEpiRowStrideBf16 * 2;
-  constexpr int kEpi = kEpi0 > kEpi1 ? kEpi0 : kEpi1;
-  constexpr int smem = kLoop > kEpi ? kLoop : kEpi;
+  constexpr int kEpi32 = 128 * kEpiRowStride * 4;  // the fp32 two-half epilogue image
+  constexpr int smem = kPPLds16 > kEpi32 ? kPPLds16 : kEpi32;
   return launch_lds<gemm256_kernel<AK, BKM, SEG>>(dim3(grid, splits), dim3(kThreads), smem, st, a);
 }
 
@@ -1518,18 +1330,10 @@ __global__ __launch_bounds__(256) void gemm_tail_reduce_k(GemmArgs p) {
   const int r = e >> 8, c = e & 255;
   const int m = tm * 256 + r, n = tn * 256 + c;
   if (m >= p.M || n >= p.N) return;
-  const float* src = p.tail_ws + (int64_t)b * p.tail_split * 65536 + e;
-  float4 a = *reinterpret_cast<const float4*>(src);
-  for (int k = 1; k < p.tail_split; ++k) {
-    const float4 v = *reinterpret_cast<const float4*>(src + (int64_t)k * 65536);
-    a.x += v.x; a.y += v.y; a.z += v.z; a.w += v.w;
-  }
+  const float4 a = tail_sum4(p.tail_ws + (int64_t)b * p.tail_split * kPPTileElems + e, p.tail_split);
   const int flags = p.flags;
   float bv[4] = {0.f, 0.f, 0.f, 0.f};
-  if (flags & kEpiBias) {
-    const uint2 braw = *reinterpret_cast<const uint2*>(p.bias + n);
-    bv[0] = lo_bf16(braw.x); bv[1] = hi_bf16(braw.x); bv[2] = lo_bf16(braw.y); bv[3] = hi_bf16(braw.y);
-  }
+  if (flags & kEpiBias) load4_16(p.bias + n, bv);
   float v[4] = {a.x * p.alpha + bv[0], a.y * p.alpha + bv[1], a.z * p.alpha + bv[2], a.w * p.alpha + bv[3]};
   const int64_t off = (int64_t)m * p.ldc + n;
   if (flags & kEpiAux)

@@ -21,6 +21,7 @@
 #include "gemm_plan.h"
 #include "launch.h"
 #include "mfma_tile.h"
+#include "pingpong256.h"
 
 using namespace pa;
 
@@ -87,12 +88,8 @@ __global__ __launch_bounds__(512, 1) void gemm_fp8_kernel(Fp8Args p) {
 
   const int nwg = p.tiles_m * p.tiles_n;
   const int pid = xcd_remap((int)blockIdx.x, nwg);
-  constexpr int GM = 8;
-  const int per_group = GM * p.tiles_n;
-  const int first_m = (pid / per_group) * GM;
-  const int gsz = min(p.tiles_m - first_m, GM);
-  const int tm = first_m + (pid % per_group) % gsz;
-  const int tn = (pid % per_group) / gsz;
+  int tm, tn;
+  tile_coords(pid, p.tiles_m, p.tiles_n, &tm, &tn);
   const int m0 = tm * kTile, n0 = tn * kTile;
 
   f32x4 acc[MR][NR];
@@ -139,14 +136,7 @@ __global__ __launch_bounds__(512, 1) void gemm_fp8_kernel(Fp8Args p) {
     const int n = ncol0 + j * 16;
     if (n >= p.N) continue;  // N % 4 == 0 (launcher)
     float bv[4] = {0.f, 0.f, 0.f, 0.f};
-    if (p.bias) {
-      const uint2 braw = *reinterpret_cast<const uint2*>(p.bias + n);
-      if (OUT_F16) {
-        bv[0] = lo_f16(braw.x); bv[1] = hi_f16(braw.x); bv[2] = lo_f16(braw.y); bv[3] = hi_f16(braw.y);
-      } else {
-        bv[0] = lo_bf16(braw.x); bv[1] = hi_bf16(braw.x); bv[2] = lo_bf16(braw.y); bv[3] = hi_bf16(braw.y);
-      }
-    }
+    if (p.bias) load4_16<OUT_F16>(p.bias + n, bv);
 #pragma unroll
     for (int i = 0; i < MR; ++i) {
       const int m = mrow0 + i * 16;
@@ -162,15 +152,14 @@ __global__ __launch_bounds__(512, 1) void gemm_fp8_kernel(Fp8Args p) {
 }
 
 // ---------------------------------------------------------------------------------------------
-// Ping-pong fp8 kernel: gemm.hip's 256x256 8-phase schedule (gemm256_kernel) at the fp8 byte geometry. A K-tile
-// of 128 fp8 is 128 bytes per row — the bf16 kernel's 64-element tile byte for byte — so the staging (four 16-KiB
-// half-tiles per K-tile, each issued six phases ahead by global_load_lds), the counted vmcnt waits, the barrier
-// stagger of the wm == 1 waves (one wave per SIMD in its MFMA cluster while the other reads LDS) and the LDS
-// swizzle are unchanged; per phase a wave runs 8 v_mfma_scale_f32_16x16x128_f8f6f4 (= the 16 bf16 16x16x32
-// MFMAs' cycles at twice the FLOPs). Fragments: lane l holds row (l & 15) and k-bytes [32 (l >> 4), +32) of the
-// 128-byte row (chunks 2g, 2g + 1). Wave (wm, wn) owns rows {wm*64.., 128+wm*64..} x cols {wn*32.., 128+wn*32..}.
-// Epilogue: alpha, bias, activation in registers, the 16-bit tile staged through LDS, 16-byte row stores
-// (N % 8 == 0). bar, vm_wait, xcd_remap, tile_coords and IntC are the bf16 kernel's own, from mfma_tile.h.
+// Ping-pong fp8 kernel: the 256x256 8-phase schedule of pingpong256.h (PPLoop, the one gemm.hip's
+// gemm256_kernel runs) at the fp8 byte geometry. A K-tile of 128 fp8 is 128 bytes per row — the bf16 kernel's
+// 64-element tile byte for byte — so the half-tiles, the issue distance, the counted vmcnt waits, the barrier
+// stagger and the LDS swizzle are that header's; per phase a wave runs 8 v_mfma_f32_16x16x128_f8f6f4 (= the 16
+// bf16 16x16x32 MFMAs' cycles at twice the FLOPs). This file supplies the fp8 policy: lane l holds row (l & 15) and
+// k-bytes [32 (l >> 4), +32) of the 128-byte row (chunks 2g, 2g + 1). The tail-slice decode, the partial store and
+// the one-pass 16-bit epilogue (alpha, bias, activation in registers, the tile staged through LDS, 16-byte row
+// stores; N % 8 == 0) are the shared ones too.
 
 // C += B-frag x A-frag on the unscaled v_mfma_f32_16x16x128_f8f6f4 (formats in cbsz / blgp); PA_FP8_SCALED_MFMA
 // selects the block-scaled form with unit E8M0 scales instead (the builtin: an extra scale operand pair).
@@ -203,21 +192,9 @@ __global__ __launch_bounds__(256) void gemm_fp8_tail_reduce_k(Fp8Args p) {
   const int r = e >> 8, c = e & 255;
   const int m = tm * 256 + r, n = tn * 256 + c;
   if (m >= p.M || n >= p.N) return;
-  const float* src = p.tail_ws + (int64_t)b * p.tail_split * 65536 + e;
-  float4 a = *reinterpret_cast<const float4*>(src);
-  for (int k = 1; k < p.tail_split; ++k) {
-    const float4 v = *reinterpret_cast<const float4*>(src + (int64_t)k * 65536);
-    a.x += v.x; a.y += v.y; a.z += v.z; a.w += v.w;
-  }
+  const float4 a = tail_sum4(p.tail_ws + (int64_t)b * p.tail_split * kPPTileElems + e, p.tail_split);
   float bq[4] = {0.f, 0.f, 0.f, 0.f};
-  if (p.bias) {
-    const uint2 braw = *reinterpret_cast<const uint2*>(p.bias + n);
-    if (OUT_F16) {
-      bq[0] = lo_f16(braw.x); bq[1] = hi_f16(braw.x); bq[2] = lo_f16(braw.y); bq[3] = hi_f16(braw.y);
-    } else {
-      bq[0] = lo_bf16(braw.x); bq[1] = hi_bf16(braw.x); bq[2] = lo_bf16(braw.y); bq[3] = hi_bf16(braw.y);
-    }
-  }
+  if (p.bias) load4_16<OUT_F16>(p.bias + n, bq);
   const float av[4] = {a.x, a.y, a.z, a.w};
   const float alpha = alpha_eff(p);
   float v[4];
@@ -228,238 +205,79 @@ __global__ __launch_bounds__(256) void gemm_fp8_tail_reduce_k(Fp8Args p) {
               : make_uint2(pack_bf16(v[0], v[1]), pack_bf16(v[2], v[3]));
 }
 
-constexpr int kPPThreads = 512;
-constexpr int kEpiRS = 264;  // 16-bit values per row of the epilogue image (528-byte rows)
+// The fp8 policy of PPLoop: one 16x16x128 MFMA per fragment pair and K-tile of 128, plain K-major bytes.
+template <int FA, int FB>
+struct PPFp8Ops {
+  static constexpr int kSub = 1;
+  using Frag = i32x8;
+  const Fp8Args& p;
+  int m0, n0, wave, lane;
+
+  static __device__ __forceinline__ Frag read_a(const char* img, int rbase, int, int lane) {
+    return frag(img, rbase, lane);
+  }
+  static __device__ __forceinline__ Frag read_b(const char* img, int rbase, int, int lane) {
+    return frag(img, rbase, lane);
+  }
+  static __device__ __forceinline__ f32x4 mma(const Frag& b, const Frag& a, f32x4 c) { return mfma8<FA, FB>(b, a, c); }
+  __device__ __forceinline__ void stage_half(int t, int h, char* dst) const {
+    const int k0 = t * kKB;
+    if (h == 0 || h == 2) stage<128, true>(p.a, p.lda, m0 + (h == 2 ? 128 : 0), p.M, k0, dst, wave, lane);
+    else stage<128, true>(p.b, p.ldb, n0 + (h == 3 ? 128 : 0), p.N, k0, dst, wave, lane);
+  }
+};
 
 template <int FA, int FB, bool OUT_F16>
 __global__ __launch_bounds__(kPPThreads, 1) void gemm_fp8_pp_kernel(Fp8Args p) {
-  constexpr int HALF = 128 * kKB;  // 16 KiB
-  constexpr int STAGE = 4 * HALF;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   const int wm = wave >> 2, wn = wave & 3;
 
-  const int bid = (int)blockIdx.x;
-  int pid;
-  float* tail_out = nullptr;
-  if (p.tail_split > 0 && bid >= p.full_tiles) {  // K slice of a tail tile
-    const int u = bid - p.full_tiles;
-    const int ks = u % p.tail_split;
-    pid = p.full_tiles + u / p.tail_split;
-    p.K /= p.tail_split;
-    p.a += (int64_t)ks * p.K;
-    p.b += (int64_t)ks * p.K;
-    tail_out = p.tail_ws + (int64_t)u * 65536;
-  } else {
-    pid = xcd_remap(bid, p.tail_split > 0 ? p.full_tiles : p.tiles_m * p.tiles_n);
+  const PPWork w = pp_work(p, (int)blockIdx.x);
+  if (w.tail_out) {  // K slice of a tail tile
+    p.a += (int64_t)w.ks * p.K;
+    p.b += (int64_t)w.ks * p.K;
   }
   int tm, tn;
-  tile_coords(pid, p.tiles_m, p.tiles_n, &tm, &tn);
+  tile_coords(w.pid, p.tiles_m, p.tiles_n, &tm, &tn);
   const int m0 = tm * kTile, n0 = tn * kTile;
-  const int nk = p.K / kKB;
-
-  auto stage_h = [&](int t, int h, char* dst) {
-    const int k0 = t * kKB;
-    if (h == 0 || h == 2) stage<128, true>(p.a, p.lda, m0 + (h == 2 ? 128 : 0), p.M, k0, dst, wave, lane);
-    else stage<128, true>(p.b, p.ldb, n0 + (h == 3 ? 128 : 0), p.N, k0, dst, wave, lane);
-  };
-  auto issue = [&](int j) {
-    const int t = j >> 2, h = j & 3;
-    stage_h(t, h, smem + (t & 1) * STAGE + h * HALF);
-  };
-  auto issue_h = [&](int t, auto hc) {
-    constexpr int h = decltype(hc)::value;
-    stage_h(t, h, smem + (t & 1) * STAGE + h * HALF);
-  };
 
   f32x4 acc[2][4][2][2];
-#pragma unroll
-  for (int a = 0; a < 2; ++a)
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-      for (int b = 0; b < 2; ++b)
-#pragma unroll
-        for (int j = 0; j < 2; ++j) acc[a][i][b][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-  const int last_j = 4 * nk - 1;
-  auto wait_for = [&](int phase, int jstar) {
-    const int issued = min(phase + 6, last_j);
-    vm_wait(2 * max(issued - jstar, 0));
-  };
-  const int npro = min(6, 4 * nk);
+  const PPFp8Ops<FA, FB> ops{p, m0, n0, wave, lane};
+  const int nk = p.K / kKB;
+  PPLoop<PPFp8Ops<FA, FB>> L{ops, smem, nk, wm, wn, lane, acc};
+  L.start();
+  int t = 0;  // the two K loops stay in the kernel: see PPLoop
 #pragma unroll 1
-  for (int j = 0; j < npro; ++j) issue(j);
-  vm_wait(2 * max(min(5, last_j) - 1, 0));
-  bar();
-  const bool lag = __builtin_amdgcn_readfirstlane(wm) == 1;
-  if (lag) bar();
-
-  i32x8 af[4], bl[2], br[2];
-  const int ar = wm * 64, bc = wn * 32;
-
-  auto ktile = [&](int t, auto steady) {
-    constexpr bool S = decltype(steady)::value;
-    const char* buf = smem + (t & 1) * STAGE;
-    const int ph = 4 * t;
-    // phase 0: read A-top + B-left; MFMA (top, L)
-#pragma unroll
-    for (int j = 0; j < 2; ++j) bl[j] = frag(buf + HALF, bc + j * 16, lane);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) af[i] = frag(buf, ar + i * 16, lane);
-    if (S) {
-      issue_h(t + 1, IntC<2>{});
-      asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-    } else {
-      if (ph + 6 <= last_j) issue(ph + 6);
-      wait_for(ph, ph + 3);
-    }
-    bar();
-    __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-      for (int j = 0; j < 2; ++j)
-        acc[0][i][0][j] =
-            mfma8<FA, FB>(bl[j], af[i], acc[0][i][0][j]);
-    __builtin_amdgcn_s_setprio(0);
-    bar();
-    // phase 1: read B-right; MFMA (top, R)
-#pragma unroll
-    for (int j = 0; j < 2; ++j) br[j] = frag(buf + 3 * HALF, bc + j * 16, lane);
-    if (S) {
-      issue_h(t + 1, IntC<3>{});
-      asm volatile("s_waitcnt vmcnt(10)" ::: "memory");
-    } else {
-      if (ph + 7 <= last_j) issue(ph + 7);
-      wait_for(ph + 1, ph + 2);
-    }
-    bar();
-    __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-      for (int j = 0; j < 2; ++j)
-        acc[0][i][1][j] =
-            mfma8<FA, FB>(br[j], af[i], acc[0][i][1][j]);
-    __builtin_amdgcn_s_setprio(0);
-    bar();
-    // phase 2: read A-bottom; MFMA (bottom, L)
-#pragma unroll
-    for (int i = 0; i < 4; ++i) af[i] = frag(buf + 2 * HALF, ar + i * 16, lane);
-    if (S) issue_h(t + 2, IntC<0>{});
-    else if (ph + 8 <= last_j) issue(ph + 8);
-    bar();
-    __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-      for (int j = 0; j < 2; ++j)
-        acc[1][i][0][j] =
-            mfma8<FA, FB>(bl[j], af[i], acc[1][i][0][j]);
-    __builtin_amdgcn_s_setprio(0);
-    bar();
-    // phase 3: wait for H0 / H1 of tile t + 1; MFMA (bottom, R)
-    if (S) {
-      issue_h(t + 2, IntC<1>{});
-      asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-    } else {
-      if (ph + 9 <= last_j) issue(ph + 9);
-      if (t + 1 < nk) wait_for(ph + 3, ph + 5);
-    }
-    bar();
-    __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-      for (int j = 0; j < 2; ++j)
-        acc[1][i][1][j] =
-            mfma8<FA, FB>(br[j], af[i], acc[1][i][1][j]);
-    __builtin_amdgcn_s_setprio(0);
-    bar();
-  };
-  const int nsteady = max(nk - 2, 0);
-  int t = 0;
+  for (; t < L.nsteady(); ++t) L.ktile(t, IntC<1>{});
 #pragma unroll 1
-  for (; t < nsteady; ++t) ktile(t, IntC<1>{});
-#pragma unroll 1
-  for (; t < nk; ++t) ktile(t, IntC<0>{});
-  if (!lag) bar();
+  for (; t < nk; ++t) L.ktile(t, IntC<0>{});
+  L.finish();
 
-  if (tail_out) {  // raw fp32 partial of this K slice, row-major 256 x 256
-    asm volatile("s_nop 7\n\ts_nop 7\n\ts_nop 7" ::: "memory");
-#pragma unroll
-    for (int bh = 0; bh < 2; ++bh)
-#pragma unroll
-      for (int j = 0; j < 2; ++j)
-#pragma unroll
-        for (int ah = 0; ah < 2; ++ah)
-#pragma unroll
-          for (int i = 0; i < 4; ++i) {
-            const int r = ah * 128 + ar + i * 16 + (lane & 15);
-            const int c = bh * 128 + bc + j * 16 + 4 * (lane >> 4);
-            const f32x4 v = acc[ah][i][bh][j];
-            *reinterpret_cast<float4*>(tail_out + r * 256 + c) = make_float4(v[0], v[1], v[2], v[3]);
-          }
-    return;
-  }
-
-  // epilogue: alpha, bias, activation in registers; the 16-bit tile through LDS ([256][264]); row stores.
   // The MFMAs are inline asm, so the compiler's hazard tracking does not see their results: wait out the
   // MFMA -> VALU read latency of the last accumulators explicitly.
   asm volatile("s_nop 7\n\ts_nop 7\n\ts_nop 7" ::: "memory");
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  uint16_t* im = reinterpret_cast<uint16_t*>(smem);
-  const float alpha = alpha_eff(p);
-  bar();
-#pragma unroll
-  for (int bh = 0; bh < 2; ++bh)
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-      const int c = bh * 128 + bc + j * 16 + 4 * (lane >> 4);
-      float bq[4] = {0.f, 0.f, 0.f, 0.f};
-      if (p.bias && n0 + c < p.N) {
-        const uint2 braw = *reinterpret_cast<const uint2*>(p.bias + n0 + c);
-        if (OUT_F16) {
-          bq[0] = lo_f16(braw.x); bq[1] = hi_f16(braw.x); bq[2] = lo_f16(braw.y); bq[3] = hi_f16(braw.y);
-        } else {
-          bq[0] = lo_bf16(braw.x); bq[1] = hi_bf16(braw.x); bq[2] = lo_bf16(braw.y); bq[3] = hi_bf16(braw.y);
-        }
-      }
-#pragma unroll
-      for (int ah = 0; ah < 2; ++ah)
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          const int r = ah * 128 + ar + i * 16 + (lane & 15);
-          float v[4];
-#pragma unroll
-          for (int e = 0; e < 4; ++e) v[e] = act_f(acc[ah][i][bh][j][e] * alpha + bq[e], p.act);
-          *reinterpret_cast<uint2*>(im + r * kEpiRS + c) =
-              OUT_F16 ? make_uint2(pack_f16(v[0], v[1]), pack_f16(v[2], v[3]))
-                      : make_uint2(pack_bf16(v[0], v[1]), pack_bf16(v[2], v[3]));
-        }
-    }
-  bar();
-  const int ecb = (tid & 31) * 8, erb = tid >> 5;
-  const int nb_ = n0 + ecb;
-  if (nb_ < p.N) {
-#pragma unroll 4
-    for (int step = 0; step < 16; ++step) {
-      const int r = step * 16 + erb;
-      const int m = m0 + r;
-      if (m >= p.M) break;
-      *reinterpret_cast<uint4*>(reinterpret_cast<uint16_t*>(p.c) + (int64_t)m * p.ldc + nb_) =
-          *reinterpret_cast<const uint4*>(im + r * kEpiRS + ecb);
-    }
+  if (w.tail_out) {
+    pp_store_partial(w.tail_out, acc, wm, wn, lane);
+    return;
   }
+
+  // epilogue: alpha, bias, activation in registers; the 16-bit tile through LDS; row stores
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  pp_epilogue16(
+      smem, acc, reinterpret_cast<uint16_t*>(p.c), p.ldc, p.M, p.N, m0, n0, alpha_eff(p), tid,
+      [&](int n, float* bq) {
+        if (p.bias && n < p.N) load4_16<OUT_F16>(p.bias + n, bq);
+      },
+      [&](float v) { return act_f(v, p.act); },
+      [](float a, float b) { return OUT_F16 ? pack_f16(a, b) : pack_bf16(a, b); });
 }
 
 // ping-pong kernel with the balanced tail pl (the plan g.full_tiles / g.tail_split were filled from)
 template <int FA, int FB, bool F16>
 int launch_pp(const Fp8Args& g, const TailPlan& pl, hipStream_t st) {
   // two 64-KiB stages; the epilogue image [256][264] x 2 B (132 KiB) reuses them and is the larger
-  constexpr int smem = (2 * 4 * 128 * kKB) > (kTile * kEpiRS * 2) ? (2 * 4 * 128 * kKB) : (kTile * kEpiRS * 2);
-  const int rc = launch_lds<gemm_fp8_pp_kernel<FA, FB, F16>>(dim3(pl.grid), dim3(kPPThreads), smem, st, g);
+  const int rc = launch_lds<gemm_fp8_pp_kernel<FA, FB, F16>>(dim3(pl.grid), dim3(kPPThreads), kPPLds16, st, g);
   if (rc || !pl.split) return rc;
   hipLaunchKernelGGL((gemm_fp8_tail_reduce_k<F16>), dim3(pl.tiles - pl.full_tiles, 64), dim3(256), 0, st, g);
   return (int)hipGetLastError();

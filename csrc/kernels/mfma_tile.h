@@ -1,7 +1,8 @@
 // LDS tile primitives of the MFMA kernels (gemm.hip, grouped_gemm.hip, gemm_fp8.hip, gemm_skinny.hip,
 // flash_attn_kernels.h): LDS-DMA, the transposing LDS read, counted waits, the fenced barrier, the image
 // swizzles with the stage / fragment-read pair each one binds, and the tile order. One definition each:
-// the stage side and the read side of a swizzle cannot drift apart between files.
+// the stage side and the read side of a swizzle cannot drift apart between files. The schedule built from them
+// for the 256x256 ping-pong kernels (gemm256_kernel, gemm_fp8_pp_kernel) is one level up, in pingpong256.h.
 #pragma once
 #include "common.h"
 

@@ -65,14 +65,23 @@ def test_fp8_gemm_matches_dequantised_reference_gpu(fa, fb, odt, act, bias, shap
     torch.testing.assert_close(out.float().cpu(), ref, rtol=tol, atol=tol * 2)
 
 
+# (shape, output dtype); the ids keep the cases' earlier names
+_EXACT_SHAPES = [(300, 264, 384), (1000, 2048, 1280), (256, 256, 128), (77, 520, 256), (513, 776, 896),
+                 (4096, 5120, 2048), (300, 264, 512), (300, 264, 640)]
+_EXACT_CASES = [pytest.param(s, torch.bfloat16, id=f"shape{i}") for i, s in enumerate(_EXACT_SHAPES)]
+_EXACT_CASES.append(pytest.param((300, 264, 384), torch.float16, id="shape8"))
+
+
 @pytest.mark.gpu
-@pytest.mark.parametrize("shape", [(300, 264, 384), (1000, 2048, 1280), (256, 256, 128), (77, 520, 256),
-                                   (513, 776, 896), (4096, 5120, 2048)])
+@pytest.mark.parametrize("shape,odt", _EXACT_CASES)
 @pytest.mark.parametrize("kernel", ["auto", "generic"])
-def test_fp8_gemm_kernels_exact_on_small_integers_gpu(shape, kernel):
+def test_fp8_gemm_kernels_exact_on_small_integers_gpu(shape, odt, kernel):
     """Both fp8 kernels — the ping-pong 256x256 schedule (auto, N % 8 == 0) and the generic one — exact on
     small-integer data: ragged M / N tiles, a single K-tile (K = 128) and two (K = 256); 4096 x 5120 (320 tiles)
-    runs the ping-pong kernel's balanced tail (64 tiles cut into 4 K slices + the reduction kernel)."""
+    runs the ping-pong kernel's balanced tail (64 tiles cut into 4 K slices + the reduction kernel). K = 512 and
+    640 are 4 and 5 K-tiles: the ping-pong loop's drain body takes the last two, so these are the first counts with
+    two and three steady iterations on alternating LDS stages. The last case is fp16 out of the ping-pong
+    epilogue: |0.5 a.b + bias| <= 0.5 * 384 * 6 + 4 = 1156, exact in fp16's range."""
     from paddlepaddle_amd.ops import fp8 as F8
     M, N, K = shape
     g = torch.Generator().manual_seed(5)
@@ -82,11 +91,12 @@ def test_fp8_gemm_kernels_exact_on_small_integers_gpu(shape, kernel):
     a8, b8 = a.to(torch.float8_e4m3fn).cuda(), b.to(torch.float8_e4m3fn).cuda()
     old = F8.set_kernel(kernel)
     try:
-        out = gemm_fp8(a8, b8, bias.to(torch.bfloat16).cuda(), 0.5, "relu", torch.bfloat16)
+        out = gemm_fp8(a8, b8, bias.to(odt).cuda(), 0.5, "relu", odt)
     finally:
         F8.set_kernel(old)
+    assert out.dtype == odt
     ref = torch.relu(0.5 * (a @ b.t()) + bias)
-    torch.testing.assert_close(out.float().cpu(), ref.to(torch.bfloat16).float(), rtol=0, atol=0)
+    torch.testing.assert_close(out.float().cpu(), ref.to(odt).float(), rtol=0, atol=0)
 
 
 @pytest.mark.gpu
