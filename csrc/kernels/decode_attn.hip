@@ -1,4 +1,4 @@
-// Paged-KV decode attention (one new query token per sequence) for gfx950, bf16 cache / fp32 math.
+// Paged-KV decode attention (one new query token per sequence) for gfx950, bf16 or int8 cache / fp32 math.
 // Reference behaviour: paddle/phi/kernels/fusion/gpu/block_attn.h (block_multihead_attention decode
 // path) and masked_multihead_attention_kernel.cu.
 //
@@ -20,10 +20,29 @@ namespace {
 
 constexpr int kLanesPerKey = 16;
 
-template <int D, int G>
+// 8 consecutive cache elements of one key as fp32: bf16 storage, or uint8 storage giving the integer u - 128
+template <typename CT> __device__ __forceinline__ void load_cache8(const CT* p, float* f);
+template <> __device__ __forceinline__ void load_cache8<uint16_t>(const uint16_t* p, float* f) {
+  load8<bf16>(reinterpret_cast<const bf16*>(p), f);
+}
+template <> __device__ __forceinline__ void load_cache8<uint8_t>(const uint8_t* p, float* f) {
+  const uint2 v = *reinterpret_cast<const uint2*>(p);
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {  // (w >> 8j) & 0xff -> v_cvt_f32_ubyte<j>
+    f[j] = (float)((v.x >> (8 * j)) & 0xffu) - 128.f;
+    f[4 + j] = (float)((v.y >> (8 * j)) & 0xffu) - 128.f;
+  }
+}
+
+// CT: cache storage, uint16_t (bf16 bits) or uint8_t (int8 + 128; k_dq / v_dq / k_cur / v_cur apply only here)
+template <int D, int G, typename CT>
 __global__ __launch_bounds__(256) void paged_decode_k(const uint16_t* __restrict__ q,      // [N, H, D]
-                                                       const uint16_t* __restrict__ kc,     // [nb, Hkv, bs, D]
-                                                       const uint16_t* __restrict__ vc,
+                                                       const CT* __restrict__ kc,           // [nb, Hkv, bs, D]
+                                                       const CT* __restrict__ vc,
+                                                       const float* __restrict__ k_dq,      // [Hkv]
+                                                       const float* __restrict__ v_dq,
+                                                       const uint16_t* __restrict__ k_cur,  // [N, Hkv, D] or null
+                                                       const uint16_t* __restrict__ v_cur,
                                                        const int* __restrict__ tables,     // [N, max_blocks]
                                                        const int* __restrict__ lens,       // [N]
                                                        float* __restrict__ part_o,         // [N, H, S, D]
@@ -34,6 +53,7 @@ __global__ __launch_bounds__(256) void paged_decode_k(const uint16_t* __restrict
                                                        float scale_log2) {
   static_assert(D == 128, "decode kernel is specialised for head_dim 128");
   constexpr int EPL = D / kLanesPerKey;  // 8 elements per lane
+  constexpr bool Q8 = sizeof(CT) == 1;
   const int n = blockIdx.x, hk = blockIdx.y, sp = blockIdx.z;
   const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63;
   const int sub = lane >> 4;            // which of the wave's 4 keys
@@ -42,6 +62,13 @@ __global__ __launch_bounds__(256) void paged_decode_k(const uint16_t* __restrict
   const int nblk = (len + bs - 1) / bs;
   const int per = (nblk + splits - 1) / splits;
   const int b0 = sp * per, b1 = min(nblk, b0 + per);
+  float kdq = 1.f, vdq = 1.f;
+  bool has_cur = false;
+  if constexpr (Q8) {
+    kdq = k_dq[hk];
+    vdq = v_dq[hk];
+    has_cur = k_cur != nullptr;
+  }
 
   // query rows of the group: lane holds elements [8 li, 8 li + 8) of each head
   float qv[G][EPL];
@@ -70,6 +97,7 @@ __global__ __launch_bounds__(256) void paged_decode_k(const uint16_t* __restrict
   for (int c0 = kbeg + 16 * w; c0 < kfin; c0 += 64) {
     float kf[4][8], vf[4][8];
     bool valid[4];
+    float ks[4], vs[4];  // int8 cache: the key's dequant scales (1 for the unquantised current token)
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
       const int key = c0 + 4 * u + sub;
@@ -78,8 +106,20 @@ __global__ __launch_bounds__(256) void paged_decode_k(const uint16_t* __restrict
       const int blk = kk / bs;
       const int64_t off = (int64_t)tables[trow + blk] * blk_stride + (int64_t)hk * head_stride +
                           (int64_t)(kk - blk * bs) * D + li * EPL;
-      load8<bf16>(reinterpret_cast<const bf16*>(kc + off), kf[u]);
-      load8<bf16>(reinterpret_cast<const bf16*>(vc + off), vf[u]);
+      if constexpr (Q8) {
+        if (has_cur && kk == len - 1) {
+          const int64_t coff = ((int64_t)n * Hkv + hk) * D + li * EPL;
+          load8<bf16>(reinterpret_cast<const bf16*>(k_cur + coff), kf[u]);
+          load8<bf16>(reinterpret_cast<const bf16*>(v_cur + coff), vf[u]);
+          ks[u] = 1.f;
+          vs[u] = 1.f;
+          continue;
+        }
+        ks[u] = kdq;
+        vs[u] = vdq;
+      }
+      load_cache8<CT>(kc + off, kf[u]);
+      load_cache8<CT>(vc + off, vf[u]);
     }
 #pragma unroll
     for (int g = 0; g < G; ++g) {
@@ -93,6 +133,7 @@ __global__ __launch_bounds__(256) void paged_decode_k(const uint16_t* __restrict
         t += __shfl_xor(t, 2, 64);
         t += __shfl_xor(t, 4, 64);
         t += __shfl_xor(t, 8, 64);
+        if constexpr (Q8) t *= ks[u];
         sc[u] = valid[u] ? t : -INFINITY;
       }
       const float mx = fmaxf(fmaxf(sc[0], sc[1]), fmaxf(sc[2], sc[3]));
@@ -103,6 +144,10 @@ __global__ __launch_bounds__(256) void paged_decode_k(const uint16_t* __restrict
 #pragma unroll
       for (int u = 0; u < 4; ++u) pe[u] = __builtin_amdgcn_exp2f(sc[u] - mn);  // exp2(-inf) = 0
       l[g] = l[g] * a + (pe[0] + pe[1]) + (pe[2] + pe[3]);
+      if constexpr (Q8) {
+#pragma unroll
+        for (int u = 0; u < 4; ++u) pe[u] *= vs[u];
+      }
 #pragma unroll
       for (int j = 0; j < EPL; ++j)
         o[g][j] = o[g][j] * a + pe[0] * vf[0][j] + pe[1] * vf[1][j] + pe[2] * vf[2][j] + pe[3] * vf[3][j];
@@ -172,25 +217,19 @@ __global__ __launch_bounds__(128) void paged_decode_combine_k(const float* __res
   }
 }
 
-}  // namespace
-
-// q [N, H, 128] bf16; caches bf16, key t of block pb / kv head h at pb*blk_stride + h*head_stride + t*128
-// (paged [num_blocks, Hkv, block_size, 128]: blk_stride = Hkv*bs*128, head_stride = bs*128; a dense
-// [B, H, max_len, 128] cache is viewed as virtual blocks with head_stride = max_len*128);
-// tables [N, max_blocks] int32; lens [N] int32 (tokens in cache incl. the current one);
-// part_o [N*H*splits*128] f32 and part_ml [N*H*splits*2] f32 workspaces; out [N, H, 128] bf16.
-PA_EXPORT int pa_paged_decode_attn(const void* q, const void* kc, const void* vc, const int* tables, const int* lens,
-                                   float* part_o, float* part_ml, void* out, int N, int H, int Hkv, int D, int bs,
-                                   int max_blocks, int splits, int64_t blk_stride, int64_t head_stride, float scale,
-                                   hipStream_t st) {
+template <typename CT>
+int launch_decode(const void* q, const void* kc, const void* vc, const float* k_dq, const float* v_dq,
+                  const void* k_cur, const void* v_cur, const int* tables, const int* lens, float* part_o,
+                  float* part_ml, void* out, int N, int H, int Hkv, int D, int bs, int max_blocks, int splits,
+                  int64_t blk_stride, int64_t head_stride, float scale, hipStream_t st) {
   if (D != 128 || H % Hkv != 0 || splits < 1) return 3;
   const int G = H / Hkv;
   const float sl2 = scale * 1.4426950408889634f;
   dim3 grid((unsigned)N, (unsigned)Hkv, (unsigned)splits);
 #define PA_DEC(GG)                                                                                                  \
-  hipLaunchKernelGGL((paged_decode_k<128, GG>), grid, dim3(256), 0, st, (const uint16_t*)q, (const uint16_t*)kc,   \
-                     (const uint16_t*)vc, tables, lens, part_o, part_ml, (uint16_t*)out, H, Hkv, bs, max_blocks, splits, blk_stride,      \
-                     head_stride, sl2)
+  hipLaunchKernelGGL((paged_decode_k<128, GG, CT>), grid, dim3(256), 0, st, (const uint16_t*)q, (const CT*)kc,      \
+                     (const CT*)vc, k_dq, v_dq, (const uint16_t*)k_cur, (const uint16_t*)v_cur, tables, lens,       \
+                     part_o, part_ml, (uint16_t*)out, H, Hkv, bs, max_blocks, splits, blk_stride, head_stride, sl2)
   switch (G) {
     case 1: PA_DEC(1); break;
     case 2: PA_DEC(2); break;
@@ -205,4 +244,33 @@ PA_EXPORT int pa_paged_decode_attn(const void* q, const void* kc, const void* vc
                      (uint16_t*)out, splits, D);
   PA_CHECK_LAUNCH();
   return 0;
+}
+
+}  // namespace
+
+// q [N, H, 128] bf16; caches bf16, key t of block pb / kv head h at pb*blk_stride + h*head_stride + t*128
+// (paged [num_blocks, Hkv, block_size, 128]: blk_stride = Hkv*bs*128, head_stride = bs*128; a dense
+// [B, H, max_len, 128] cache is viewed as virtual blocks with head_stride = max_len*128);
+// tables [N, max_blocks] int32; lens [N] int32 (tokens in cache incl. the current one);
+// part_o [N*H*splits*128] f32 and part_ml [N*H*splits*2] f32 workspaces; out [N, H, 128] bf16.
+PA_EXPORT int pa_paged_decode_attn(const void* q, const void* kc, const void* vc, const int* tables, const int* lens,
+                                   float* part_o, float* part_ml, void* out, int N, int H, int Hkv, int D, int bs,
+                                   int max_blocks, int splits, int64_t blk_stride, int64_t head_stride, float scale,
+                                   hipStream_t st) {
+  return launch_decode<uint16_t>(q, kc, vc, nullptr, nullptr, nullptr, nullptr, tables, lens, part_o, part_ml, out, N,
+                                 H, Hkv, D, bs, max_blocks, splits, blk_stride, head_stride, scale, st);
+}
+
+// The same over uint8 caches (int8 value + 128): a cached element is (u - 128) * k_dq[kv head] (v_dq for V), the
+// [Hkv] fp32 scales read on the device. k_cur / v_cur [N, Hkv, 128] bf16 (both or neither): key lens[n] - 1 of
+// sequence n is taken from them unquantised and its cache slot is not read. Strides in elements (= bytes).
+PA_EXPORT int pa_paged_decode_attn_q8(const void* q, const void* kc, const void* vc, const float* k_dq,
+                                      const float* v_dq, const void* k_cur, const void* v_cur, const int* tables,
+                                      const int* lens, float* part_o, float* part_ml, void* out, int N, int H,
+                                      int Hkv, int D, int bs, int max_blocks, int splits, int64_t blk_stride,
+                                      int64_t head_stride, float scale, hipStream_t st) {
+  if (k_dq == nullptr || v_dq == nullptr || (k_cur == nullptr) != (v_cur == nullptr)) return 5;
+  if (blk_stride % 8 != 0 || head_stride % 8 != 0) return 6;  // 8-byte row loads
+  return launch_decode<uint8_t>(q, kc, vc, k_dq, v_dq, k_cur, v_cur, tables, lens, part_o, part_ml, out, N, H, Hkv, D,
+                                bs, max_blocks, splits, blk_stride, head_stride, scale, st);
 }

@@ -9,6 +9,9 @@
 // decode_rope_cache_k: the QKV projection output of one token per sequence, [B, (H + 2*Hkv) * D], is
 //   rotated (NeoX halves) and split in one pass: rotated Q -> q_out [B, H, D]; rotated K and V -> the dense
 //   caches [Bc, Hkv, Lc, D] at the device-side position *pos (no host read: hipGraph-capturable).
+//   pa_decode_rope_cache_q8 instantiates it for uint8 caches (int8 + 128): the value the 16-bit kernel would have
+//   stored, x, is written as clamp(sign(z) floor(|z| + 0.5), -127, 127) + 128 with z = x * scale[kv head]
+//   (block_attn.h quant_round_type 1), the [Hkv] quant scales read on the device.
 #include "common.h"
 
 using namespace pa;
@@ -106,14 +109,36 @@ __global__ __launch_bounds__(256) void add_rms_norm_wg_k(const T* x, const T* __
   }
 }
 
+// 8 cache elements: as T, or (uint8 cache) the T-rounded values quantised with ``qs``. The product and the + 0.5
+// are single rounded operations (no FMA contraction), so exact .5 ties fall where torch's formula puts them.
+template <typename T, typename CT>
+__device__ __forceinline__ void store_cache8(CT* p, const float* f, float qs) {
+  if constexpr (sizeof(CT) == 1) {
+    uint32_t w[2] = {0u, 0u};
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const float z = __fmul_rn(to_f(from_f<T>(f[j])), qs);
+      float r = copysignf(floorf(__fadd_rn(fabsf(z), 0.5f)), z);
+      r = fminf(fmaxf(r, -127.f), 127.f);
+      w[j >> 2] |= (uint32_t)((int)r + 128) << (8 * (j & 3));
+    }
+    *reinterpret_cast<uint2*>(p) = make_uint2(w[0], w[1]);
+  } else {
+    store8<T>(p, f);
+  }
+}
+
 // work item: (b, head, 8-lane chunk). Q and K heads: NeoX rotation of 8 elements of the first half and the
-// matching 8 of the second half; V heads: a copy of 8 elements.
-template <typename T>
+// matching 8 of the second half; V heads: a copy of 8 elements. CT: the caches' storage, T or uint8_t (then
+// k_q / v_q are the [Hkv] quant scales).
+template <typename T, typename CT>
 __global__ __launch_bounds__(256) void decode_rope_cache_k(const T* __restrict__ qkv, int64_t ld,
                                                            const float* __restrict__ cs, const float* __restrict__ sn,
                                                            const int64_t* __restrict__ pos, T* __restrict__ q_out,
-                                                           T* __restrict__ kc, T* __restrict__ vc, int B, int H,
-                                                           int Hkv, int D, int64_t Lc) {
+                                                           CT* __restrict__ kc, CT* __restrict__ vc,
+                                                           const float* __restrict__ k_q,
+                                                           const float* __restrict__ v_q, int B, int H, int Hkv,
+                                                           int D, int64_t Lc) {
   const int rot = D / 16, cp = D / 8;
   const int per_b = (H + Hkv) * rot + Hkv * cp;
   const int64_t n = (int64_t)B * per_b;
@@ -134,20 +159,25 @@ __global__ __launch_bounds__(256) void decode_rope_cache_k(const T* __restrict__
         oa[j] = a[j] * cs[d0 + j] - c[j] * sn[d0 + j];
         ob[j] = c[j] * cs[d1 + j] + a[j] * sn[d1 + j];
       }
-      T* dst;
       if (head < H) {
-        dst = q_out + ((int64_t)b * H + head) * D;
+        T* dst = q_out + ((int64_t)b * H + head) * D;
+        store8<T>(dst + d0, oa);
+        store8<T>(dst + d1, ob);
       } else {
-        dst = kc + (((int64_t)b * Hkv + (head - H)) * Lc + p) * D;
+        CT* dst = kc + (((int64_t)b * Hkv + (head - H)) * Lc + p) * D;
+        float qs = 1.f;
+        if constexpr (sizeof(CT) == 1) qs = k_q[head - H];
+        store_cache8<T, CT>(dst + d0, oa, qs);
+        store_cache8<T, CT>(dst + d1, ob, qs);
       }
-      store8<T>(dst + d0, oa);
-      store8<T>(dst + d1, ob);
     } else {
       t -= (H + Hkv) * rot;
       const int head = t / cp, k = t % cp;
       float a[8];
       load8<T>(row + (int64_t)(H + Hkv + head) * D + k * 8, a);
-      store8<T>(vc + (((int64_t)b * Hkv + head) * Lc + p) * D + k * 8, a);
+      float qs = 1.f;
+      if constexpr (sizeof(CT) == 1) qs = v_q[head];
+      store_cache8<T, CT>(vc + (((int64_t)b * Hkv + head) * Lc + p) * D + k * 8, a, qs);
     }
   }
 }
@@ -195,9 +225,24 @@ PA_EXPORT int pa_decode_rope_cache(const void* qkv, int64_t ld, const float* cs,
                                    hipStream_t st) {
   if (D % 16 != 0) return 2;
   const int64_t n = (int64_t)B * ((H + Hkv) * (D / 16) + Hkv * (D / 8));
-  PA_DISPATCH_DTYPE(dtype, T, hipLaunchKernelGGL((decode_rope_cache_k<T>), dim3(launch_grid(n)), dim3(256), 0, st,
-                                                 (const T*)qkv, ld, cs, sn, pos, (T*)q_out, (T*)kc, (T*)vc, B, H, Hkv,
-                                                 D, Lc));
+  PA_DISPATCH_DTYPE(dtype, T, hipLaunchKernelGGL((decode_rope_cache_k<T, T>), dim3(launch_grid(n)), dim3(256), 0, st,
+                                                 (const T*)qkv, ld, cs, sn, pos, (T*)q_out, (T*)kc, (T*)vc, nullptr,
+                                                 nullptr, B, H, Hkv, D, Lc));
+  PA_CHECK_LAUNCH();
+  return 0;
+}
+
+// uint8 caches [Bc, Hkv, Lc, D]; k_q / v_q: [Hkv] fp32 quant scales in device memory. q_out as above, bit for bit.
+PA_EXPORT int pa_decode_rope_cache_q8(const void* qkv, int64_t ld, const float* cs, const float* sn,
+                                      const int64_t* pos, void* q_out, void* kc, void* vc, const float* k_q,
+                                      const float* v_q, int B, int H, int Hkv, int D, int64_t Lc, int dtype,
+                                      hipStream_t st) {
+  if (D % 16 != 0 || k_q == nullptr || v_q == nullptr) return 2;
+  if (dtype == pa::kF32) return 2;  // the cache holds the quantised 16-bit value
+  const int64_t n = (int64_t)B * ((H + Hkv) * (D / 16) + Hkv * (D / 8));
+  PA_DISPATCH_DTYPE(dtype, T, hipLaunchKernelGGL((decode_rope_cache_k<T, uint8_t>), dim3(launch_grid(n)), dim3(256), 0,
+                                                 st, (const T*)qkv, ld, cs, sn, pos, (T*)q_out, (uint8_t*)kc,
+                                                 (uint8_t*)vc, k_q, v_q, B, H, Hkv, D, Lc));
   PA_CHECK_LAUNCH();
   return 0;
 }

@@ -91,6 +91,11 @@ PA_EXPORT int pa_paged_decode_attn(const void* q, const void* kc, const void* vc
                                    float* part_o, float* part_ml, void* out, int N, int H, int Hkv, int D, int bs,
                                    int max_blocks, int splits, int64_t blk_stride, int64_t head_stride, float scale,
                                    hipStream_t st);
+PA_EXPORT int pa_paged_decode_attn_q8(const void* q, const void* kc, const void* vc, const float* k_dq,
+                                      const float* v_dq, const void* k_cur, const void* v_cur, const int* tables,
+                                      const int* lens, float* part_o, float* part_ml, void* out, int N, int H,
+                                      int Hkv, int D, int bs, int max_blocks, int splits, int64_t blk_stride,
+                                      int64_t head_stride, float scale, hipStream_t st);
 
 // decode_fused.hip
 PA_EXPORT int pa_add_rms_norm_fwd(const void* x, const void* r, const void* w, void* s_out, void* y, int64_t rows,
@@ -98,6 +103,10 @@ PA_EXPORT int pa_add_rms_norm_fwd(const void* x, const void* r, const void* w, v
 PA_EXPORT int pa_decode_rope_cache(const void* qkv, int64_t ld, const float* cs, const float* sn, const int64_t* pos,
                                    void* q_out, void* kc, void* vc, int B, int H, int Hkv, int D, int64_t Lc,
                                    int dtype, hipStream_t st);
+PA_EXPORT int pa_decode_rope_cache_q8(const void* qkv, int64_t ld, const float* cs, const float* sn,
+                                      const int64_t* pos, void* q_out, void* kc, void* vc, const float* k_q,
+                                      const float* v_q, int B, int H, int Hkv, int D, int64_t Lc, int dtype,
+                                      hipStream_t st);
 
 // dwconv.hip
 PA_EXPORT int pa_dwconv_fwd(const void* x, const void* wt, const void* bias, void* y, const int* shape, int dtype,

@@ -778,15 +778,21 @@ def block_multihead_attention(qkv, key_cache, value_cache, seq_lens_encoder, seq
         if max_dec is not None:
             ml = max_dec + 1 + P
         kd, vd = kc, vc
-        if quant_cache:  # dequantised view of the cache; the step's own rows stay exact
+        if quant_cache:
             kdq = _t(cache_k_dequant_scales).float().reshape(-1, Hk)[0].to(dev)  # dynamic: row 0, as the reference
             vdq = _t(cache_v_dequant_scales).float().reshape(-1, Hk)[0].to(dev)
+        if quant_cache and tgt_mask is not None:  # dequantised view of the cache; the step's own rows stay exact
             kd = ((kc.float() - 128.0) * kdq.view(1, -1, 1, 1)).to(adt)
             vd = ((vc.float() - 128.0) * vdq.view(1, -1, 1, 1)).to(adt)
             kd[blk, :, pos % bs] = k.to(adt)
             vd[blk, :, pos % bs] = v.to(adt)
         if tgt_mask is not None:
             o_d = _blha_decode_math(q.to(adt), kd, vd, bt[bid], lens, _t(tgt_mask)[bid])
+        elif quant_cache:
+            # the decode kernel reads the uint8 cache itself; each token's own K / V go in unquantised. (A prefill
+            # token riding along reads position 0 of its sequence as its own row; o_p replaces its result below.)
+            o_d = _ops.paged_decode_attention(q.to(adt), kc, vc, bt[bid], lens, max_len=ml, k_dequant=kdq,
+                                              v_dequant=vdq, k_cur=k.to(adt), v_cur=v.to(adt))
         else:
             o_d = _ops.paged_decode_attention(q.to(adt), kd, vd, bt[bid], lens, max_len=ml)
         o = o_d if o is None else torch.where(prefill_tok.view(T, 1, 1), o, o_d)

@@ -163,6 +163,29 @@ class _Rope:
         return self.cos, self.sin
 
 
+class Int8KVCache:
+    """One layer's int8 KV cache: ``k`` / ``v`` uint8 [B, Hkv, max_len, D] (int8 value + 128) and the per-kv-head
+    fp32 [Hkv] device tensors ``k_scale`` / ``v_scale`` (quantisation) and ``k_dequant`` / ``v_dequant``. The
+    prefill sets the scales from the prompt (127 / max|x| per kv head) on the device; decode steps reuse them, so
+    later values beyond the prompt's range clamp."""
+
+    def __init__(self, shape, device):
+        self.k = torch.full(shape, 128, dtype=torch.uint8, device=device)
+        self.v = torch.full(shape, 128, dtype=torch.uint8, device=device)
+        Hkv = shape[1]
+        self.k_scale, self.v_scale, self.k_dequant, self.v_dequant = (
+            torch.ones(Hkv, dtype=torch.float32, device=device) for _ in range(4))
+
+    def write_prefill(self, k, v):
+        """k, v [B, S, Hkv, D]: the prompt's rotated K and V. Sets the scales and stores positions 0 .. S-1."""
+        B, S = k.shape[0], k.shape[1]
+        for x, cache, sc, dq in ((k, self.k, self.k_scale, self.k_dequant), (v, self.v, self.v_scale, self.v_dequant)):
+            amax = x.float().abs().amax(dim=(0, 1, 3)).clamp_min(1e-20)
+            sc.copy_(127.0 / amax)
+            dq.copy_(amax / 127.0)
+            cache[:B, :, :S].copy_(_ops.quantize_kv_int8(x, sc).transpose(1, 2))
+
+
 def _core(attn, fn, *ts):
     """The attention core ``fn(*ts)`` (torch tensors), checkpointed when the layer's recompute granularity is
     core_attn (``attn._rc_core``): only its inputs are kept, the core is re-run in backward."""
@@ -239,6 +262,11 @@ class LlamaAttention(nn.Layer):
         o-projection GEMM on the plain training path — _proj_res)."""
         if cache is None and getattr(self, "bs", None) is not None and x._t.dim() == 2:
             return _add_res(self._forward_sp(x), residual)
+        if isinstance(cache, Int8KVCache) and not isinstance(pos, torch.Tensor) and pos > 0:
+            if x._t.shape[1] != 1:
+                raise NotImplementedError("LlamaAttention: a second prefill chunk (pos > 0, more than one token) on "
+                                          "an int8 KV cache")
+            pos = torch.full((1,), pos, dtype=torch.int64, device=x._t.device)  # a decode step: the int8 kernels
         if cache is not None and isinstance(pos, torch.Tensor):
             return _add_res(self._decode_step(x, cache, pos), residual)
         if cache is None and self.cfg.sep_parallel_degree <= 1 and self.cfg.fused_qkv_attention:
@@ -257,7 +285,12 @@ class LlamaAttention(nn.Layer):
         cos, sin = self.rope.tables(pos + S, q.device)
         q = _ops.apply_rotary(q, cos[pos:pos + S], sin[pos:pos + S])
         k = _ops.apply_rotary(k, cos[pos:pos + S], sin[pos:pos + S])
-        if cache is not None:
+        if isinstance(cache, Int8KVCache):
+            # prefill (pos 0): attention over the prompt's unquantised K / V; the cache gets them quantised with
+            # scales taken from this prompt
+            cache.write_prefill(k, v)
+            causal = S > 1
+        elif cache is not None:
             # cache layout [B, Hkv, max_len, D] (the decode kernel's dense layout); prefill reads it back
             # as a strided [B, S, Hkv, D] view
             kc, vc = cache
@@ -289,7 +322,8 @@ class LlamaAttention(nn.Layer):
         read, so the step can be captured once into a hipGraph and replayed for every token. One fused
         kernel rotates Q/K with the RoPE rows at pos_t, splits the QKV projection and writes K/V into the
         dense cache at pos_t; attention is the flash-decoding HIP kernel over the first pos_t + 1 tokens."""
-        kc, vc = cache
+        q8 = isinstance(cache, Int8KVCache)
+        kc, vc = (cache.k, cache.v) if q8 else cache
         t = self.qkv_proj(x)._t
         B = t.shape[0]
         q = t  # dtype / device carrier for the context below
@@ -303,6 +337,12 @@ class LlamaAttention(nn.Layer):
             _DECODE_CTX.clear()
             _DECODE_CTX[id(pos_t)] = ctx
         _, _, cs, sn, lens = ctx
+        if q8:  # the token's K / V are stored quantised and read back quantised, like at every later step
+            q = _ops.decode_rope_cache(t.reshape(B, -1), self.H, self.Hkv, self.D, cs, sn, pos_t, kc, vc,
+                                       k_scale=cache.k_scale, v_scale=cache.v_scale)
+            o = _ops.dense_decode_attention(q, kc[:B], vc[:B], lens, max_len=Lc, k_dequant=cache.k_dequant,
+                                            v_dequant=cache.v_dequant)
+            return self.o_proj(_wrap(o.reshape(B, 1, self.H * self.D)))
         q = _ops.decode_rope_cache(t.reshape(B, -1), self.H, self.Hkv, self.D, cs, sn, pos_t, kc, vc)
         o = _ops.dense_decode_attention(q, kc[:B], vc[:B], lens, max_len=Lc)
         return self.o_proj(_wrap(o.reshape(B, 1, self.H * self.D)))
@@ -461,27 +501,35 @@ class LlamaForCausalLM(nn.Layer):
         return self._logits(self.llama(input_ids, caches, pos))
 
     # ------------------------------------------------------------------ generation
-    def new_cache(self, batch, max_length):
+    def new_cache(self, batch, max_length, kv_dtype=None):
+        """Per-layer KV caches [batch, Hkv, max_length, D]: (k, v) in the parameters' dtype, or with
+        ``kv_dtype="int8"`` one ``Int8KVCache`` per layer (half the bytes per cached token)."""
         cfg = self.config
         p = next(iter(self.parameters()))
         Hkv = max(cfg.num_key_value_heads // max(cfg.tensor_parallel_degree, 1), 1)
         max_length = -(-max_length // 64) * 64  # whole 64-token blocks for the decode kernel
         shape = (batch, Hkv, max_length, cfg.head_dim)
+        if kv_dtype is not None:
+            if str(kv_dtype) != "int8":
+                raise ValueError(f"new_cache: kv_dtype must be None or 'int8', got {kv_dtype!r}")
+            return [Int8KVCache(shape, p._t.device) for _ in range(cfg.num_hidden_layers)]
         return [(torch.zeros(shape, dtype=p._t.dtype, device=p._t.device),
                  torch.zeros(shape, dtype=p._t.dtype, device=p._t.device)) for _ in range(cfg.num_hidden_layers)]
 
     @torch.no_grad()
     def generate(self, input_ids, max_new_tokens=16, decode_strategy="greedy_search", temperature=1.0, top_k=0,
-                 top_p=1.0, eos_token_id=None, use_graph=False):
+                 top_p=1.0, eos_token_id=None, use_graph=False, kv_cache_dtype=None):
         """Prefill once, then one token per step against the KV cache. Returns (ids, scores).
+        ``kv_cache_dtype="int8"``: the cache holds int8 K / V with per-kv-head scales taken from the prompt
+        (``Int8KVCache``); the decode steps write and read it through the int8 HIP kernels.
         ``use_graph`` (greedy, HIP device): the decode step is captured once into a hipGraph and replayed
         per token — decode is launch-bound at serving batch sizes, the graph turns ~15 launches per layer
         into one submission per token."""
         ids = input_ids._t
         B, S = ids.shape
         if use_graph and decode_strategy == "greedy_search" and ids.is_cuda:
-            return self._generate_graph(ids, max_new_tokens, eos_token_id)
-        caches = self.new_cache(B, S + max_new_tokens)
+            return self._generate_graph(ids, max_new_tokens, eos_token_id, kv_cache_dtype)
+        caches = self.new_cache(B, S + max_new_tokens, kv_cache_dtype)
         logits = self.forward(_wrap(ids), caches, 0)._t[:, -1].float()
         out, scores = [], []
         eos = self.config.eos_token_id if eos_token_id is None else eos_token_id
@@ -520,9 +568,9 @@ class LlamaForCausalLM(nn.Layer):
             x = layer(x, caches[i], pos_t)
         return self._logits(self.llama.norm(x))._t[:, -1].float()
 
-    def _generate_graph(self, ids, max_new_tokens, eos_token_id):
+    def _generate_graph(self, ids, max_new_tokens, eos_token_id, kv_cache_dtype=None):
         B, S = ids.shape
-        caches = self.new_cache(B, S + max_new_tokens)
+        caches = self.new_cache(B, S + max_new_tokens, kv_cache_dtype)
         logits = self.forward(_wrap(ids), caches, 0)._t[:, -1].float()
         eos = self.config.eos_token_id if eos_token_id is None else eos_token_id
         tok = torch.empty(B, 1, dtype=ids.dtype, device=ids.device)

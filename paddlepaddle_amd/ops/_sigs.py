@@ -65,6 +65,7 @@ SIGS = {
     "pa_fa_fm_stats": [_vp, _i32, _i32, _i32, _i32, _i32, _i64, _i64, _i32, _vp, _vp],
     "pa_paged_decode_attn": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32,
                              _i64, _i64, _f32, _vp],
+    "pa_paged_decode_attn_q8": [_vp] * 12 + [_i32, _i32, _i32, _i32, _i32, _i32, _i32, _i64, _i64, _f32, _vp],
     # gemm epilogue companions
     "pa_colsum": [_vp, _vp, _vp, _i64, _i64, _i32, _vp],
     "pa_dwconv_fwd": [_vp, _vp, _vp, _vp, _vp, _i32, _vp],
@@ -142,6 +143,8 @@ SIGS = {
     # fused decode step
     "pa_add_rms_norm_fwd": [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _f32, _i32, _vp],
     "pa_decode_rope_cache": [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i64, _i32, _vp],
+    "pa_decode_rope_cache_q8": [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i64, _i32,
+                                _vp],
     # pooling
     "pa_maxpool_nhwc_fwd": [_vp, _vp, _vp] + [_i32] * 10 + [_vp],
     "pa_maxpool_nhwc_bwd": [_vp, _vp, _vp] + [_i32] * 10 + [_vp],

@@ -527,13 +527,16 @@ def _decode_splits(N, Hkv, max_len, bs):
 
 def _decode_hip_ok(q, key_cache, value_cache, Hkv):
     N, H, D = q.shape
-    return (L.hip_enabled_for(q) and L.has("pa_paged_decode_attn") and q.dtype == torch.bfloat16
-            and key_cache.dtype == torch.bfloat16 and value_cache.dtype == torch.bfloat16 and D == 128
+    cdt = key_cache.dtype
+    name = "pa_paged_decode_attn_q8" if cdt == torch.uint8 else "pa_paged_decode_attn"
+    return (L.hip_enabled_for(q) and L.has(name) and q.dtype == torch.bfloat16
+            and cdt in (torch.bfloat16, torch.uint8) and value_cache.dtype == cdt and D == 128
             and H % Hkv == 0 and H // Hkv in (1, 2, 4, 8) and key_cache.is_contiguous()
             and value_cache.is_contiguous())
 
 
-def _decode_launch(q, kc, vc, tables, lens, Hkv, bs, blk_stride, head_stride, scale, max_len):
+def _decode_launch(q, kc, vc, tables, lens, Hkv, bs, blk_stride, head_stride, scale, max_len, q8=None):
+    """``q8``: (k_dequant, v_dequant, k_cur, v_cur) for uint8 caches."""
     N, H, D = q.shape
     q = q.contiguous()
     tables = tables.to(torch.int32).contiguous()
@@ -543,10 +546,64 @@ def _decode_launch(q, kc, vc, tables, lens, Hkv, bs, blk_stride, head_stride, sc
     part_o = torch.empty(N * H * splits * D, dtype=torch.float32, device=q.device)
     part_ml = torch.empty(N * H * splits * 2, dtype=torch.float32, device=q.device)
     out = torch.empty_like(q)
+    if q8 is not None:
+        kdq, vdq, k_cur, v_cur = q8
+        L.call("pa_paged_decode_attn_q8", L.ptr(q), L.ptr(kc), L.ptr(vc), L.ptr(kdq), L.ptr(vdq), L.ptr(k_cur),
+               L.ptr(v_cur), L.ptr(tables), L.ptr(lens32), L.ptr(part_o), L.ptr(part_ml), L.ptr(out), N, H, Hkv, D,
+               bs, max_blocks, splits, int(blk_stride), int(head_stride), float(scale), L.stream_ptr())
+        return out
     L.call("pa_paged_decode_attn", L.ptr(q), L.ptr(kc), L.ptr(vc), L.ptr(tables), L.ptr(lens32), L.ptr(part_o),
            L.ptr(part_ml), L.ptr(out), N, H, Hkv, D, bs, max_blocks, splits, int(blk_stride), int(head_stride),
            float(scale), L.stream_ptr())
     return out
+
+
+def _q8_args(q, key_cache, value_cache, Hkv, k_dequant, v_dequant, k_cur, v_cur):
+    """Checks the int8-cache arguments of the decode wrappers. None for a float cache without them, else
+    (k_dequant, v_dequant) fp32 [Hkv] on q's device and (k_cur, v_cur) [N, Hkv, D] in q's dtype or (None, None)."""
+    quant = key_cache.dtype == torch.uint8
+    if quant != (value_cache.dtype == torch.uint8):
+        raise ValueError("decode attention: key and value cache must both be uint8 (int8 + 128) or both float")
+    given = [a is not None for a in (k_dequant, v_dequant, k_cur, v_cur)]
+    if not quant:
+        if any(given):
+            raise ValueError("decode attention: k_dequant / v_dequant / k_cur / v_cur go with uint8 (int8 + 128) "
+                             f"caches, got a {key_cache.dtype} cache")
+        return None
+    if not (given[0] and given[1]):
+        raise ValueError("decode attention: uint8 caches need k_dequant and v_dequant ([kv_heads] dequant scales)")
+    if given[2] != given[3]:
+        raise ValueError("decode attention: k_cur and v_cur go together")
+    N, H, D = q.shape
+    sc = []
+    for t in (k_dequant, v_dequant):
+        if t.numel() != Hkv:
+            raise ValueError(f"decode attention: dequant scales must hold {Hkv} values (one per kv head), got "
+                             f"{list(t.shape)}")
+        if t.dtype != torch.float32 or t.device != q.device or not t.is_contiguous():
+            t = t.to(device=q.device, dtype=torch.float32).contiguous()
+        sc.append(t.reshape(Hkv))
+    cur = [None, None]
+    if given[2]:
+        for i, t in enumerate((k_cur, v_cur)):
+            if tuple(t.shape) != (N, Hkv, D):
+                raise ValueError(f"decode attention: k_cur / v_cur must be [N, kv_heads, D] = {[N, Hkv, D]}, got "
+                                 f"{list(t.shape)}")
+            cur[i] = t.to(q.dtype).contiguous()
+    return sc[0], sc[1], cur[0], cur[1]
+
+
+def _dequant_gathered(K, V, lens, q8):
+    """K, V uint8 [N, Hkv, L, D] (the keys of each sequence, already gathered) -> fp32 (u - 128) * dequant, with key
+    lens[n] - 1 replaced by k_cur / v_cur when given."""
+    kdq, vdq, k_cur, v_cur = q8
+    K = (K.float() - 128.0) * kdq.view(1, -1, 1, 1)
+    V = (V.float() - 128.0) * vdq.view(1, -1, 1, 1)
+    if k_cur is not None:
+        last = (torch.arange(K.shape[2], device=K.device)[None] == (lens.long()[:, None] - 1))[:, None, :, None]
+        K = torch.where(last, k_cur.float().unsqueeze(2), K)
+        V = torch.where(last, v_cur.float().unsqueeze(2), V)
+    return K, V
 
 
 @static_op
@@ -558,19 +615,34 @@ def attention_bhsd(q, k, v, scale=None, mask=None, causal=False):
 
 
 @static_op
-def paged_decode_attention(q, key_cache, value_cache, block_tables, lens, scale=None, max_len=None):
+def paged_decode_attention(q, key_cache, value_cache, block_tables, lens, scale=None, max_len=None, k_dequant=None,
+                           v_dequant=None, k_cur=None, v_cur=None):
     """One-token-per-sequence attention over a paged KV cache (block_multihead_attention decode).
     q [N,H,D]; caches [num_blocks,Hkv,block_size,D]; block_tables [N,max_blocks]; lens [N] cached
     tokens incl. the current one. HIP flash-decoding kernel (csrc/kernels/decode_attn.hip) for bf16,
     head_dim 128; otherwise the fp32 reference. ``max_len`` bounds lens (host hint for the split count;
-    defaults to the block-table capacity, so no device sync)."""
+    defaults to the block-table capacity, so no device sync).
+    uint8 caches (int8 + 128) need ``k_dequant`` / ``v_dequant`` ([kv_heads] fp32; an element is (u - 128) * scale)
+    and run the same kernel reading bytes, the scales taken from device memory; ``k_cur`` / ``v_cur`` [N, Hkv, D]
+    then stand in for key lens - 1 unquantised (its cache slot is not read). The fallback dequantises only the
+    blocks the tables name."""
     N, H, D = q.shape
     _, Hkv, bs, _ = key_cache.shape
     scale = 1.0 / math.sqrt(D) if scale is None else float(scale)
+    q8 = _q8_args(q, key_cache, value_cache, Hkv, k_dequant, v_dequant, k_cur, v_cur)
     if not _decode_hip_ok(q, key_cache, value_cache, Hkv):
-        return paged_decode_reference(q, key_cache, value_cache, block_tables, lens, scale)
+        if q8 is None:
+            return paged_decode_reference(q, key_cache, value_cache, block_tables, lens, scale)
+        nblk = block_tables.shape[1]
+        tab = block_tables.long()
+        K = key_cache[tab].permute(0, 2, 1, 3, 4).reshape(N, Hkv, nblk * bs, D)
+        V = value_cache[tab].permute(0, 2, 1, 3, 4).reshape(N, Hkv, nblk * bs, D)
+        K, V = _dequant_gathered(K, V, lens, q8)
+        valid = torch.arange(nblk * bs, device=q.device)[None] < lens.long()[:, None]
+        return _decode_math(q, K, V, valid, scale)
     ml = block_tables.shape[1] * bs if max_len is None else int(max_len)
-    return _decode_launch(q, key_cache, value_cache, block_tables, lens, Hkv, bs, Hkv * bs * D, bs * D, scale, ml)
+    return _decode_launch(q, key_cache, value_cache, block_tables, lens, Hkv, bs, Hkv * bs * D, bs * D, scale, ml,
+                          q8)
 
 
 _VBLK = 64  # virtual block size when a dense cache is streamed by the paged kernel
@@ -580,15 +652,21 @@ _DENSE_TABLES = {}
 
 
 @static_op
-def dense_decode_attention(q, key_cache, value_cache, lens, scale=None, max_len=None):
+def dense_decode_attention(q, key_cache, value_cache, lens, scale=None, max_len=None, k_dequant=None,
+                           v_dequant=None, k_cur=None, v_cur=None):
     """Decode attention over a dense per-sequence cache [B,Hkv,max_len,D] (masked_multihead_attention
     layout). The same HIP kernel streams it as virtual 64-token blocks: block j of sequence b starts at
-    b*Hkv*max_len*D + j*64*D and heads are max_len*D apart, so the block table is just b*Hkv*nb + j."""
+    b*Hkv*max_len*D + j*64*D and heads are max_len*D apart, so the block table is just b*Hkv*nb + j.
+    uint8 caches: ``k_dequant`` / ``v_dequant`` / ``k_cur`` / ``v_cur`` as for paged_decode_attention."""
     N, H, D = q.shape
     B, Hkv, Lc, _ = key_cache.shape
     scale = 1.0 / math.sqrt(D) if scale is None else float(scale)
+    q8 = _q8_args(q, key_cache, value_cache, Hkv, k_dequant, v_dequant, k_cur, v_cur)
     if not _decode_hip_ok(q, key_cache, value_cache, Hkv) or Lc % _VBLK != 0:
         valid = torch.arange(Lc, device=q.device)[None] < lens.long()[:, None]
+        if q8 is not None:
+            K, V = _dequant_gathered(key_cache[:N], value_cache[:N], lens, q8)
+            return _decode_math(q, K, V, valid, scale)
         return _decode_math(q, key_cache, value_cache, valid, scale)
     nb = Lc // _VBLK
     key = (N, Hkv, nb, q.device)
@@ -600,4 +678,4 @@ def dense_decode_attention(q, key_cache, value_cache, lens, scale=None, max_len=
             _DENSE_TABLES.clear()
         _DENSE_TABLES[key] = tables
     ml = Lc if max_len is None else int(max_len)
-    return _decode_launch(q, key_cache, value_cache, tables, lens, Hkv, _VBLK, _VBLK * D, Lc * D, scale, ml)
+    return _decode_launch(q, key_cache, value_cache, tables, lens, Hkv, _VBLK, _VBLK * D, Lc * D, scale, ml, q8)

@@ -74,11 +74,47 @@ def rope_tables(seq_len, dim, base=10000.0, device=None, neox=True):
     return emb.cos(), emb.sin()
 
 
-def decode_rope_cache(qkv, H, Hkv, D, cos_row, sin_row, pos_t, k_cache, v_cache):
+def quantize_kv_int8(x, scale):
+    """The int8 KV-cache byte of x [..., Hkv, D] under per-kv-head quant scales [Hkv] (fp32): z = x * scale in fp32,
+    clamp(sign(z) * floor(|z| + 0.5), -127, 127) + 128 as uint8 (the reference's quant_round_type 1; read back as
+    (u - 128) * dequant_scale)."""
+    z = x.float() * scale.float().reshape(-1, 1)
+    z = torch.sign(z) * torch.floor(z.abs() + 0.5)
+    return (z.clamp(-127.0, 127.0) + 128.0).to(torch.uint8)
+
+
+def decode_rope_cache(qkv, H, Hkv, D, cos_row, sin_row, pos_t, k_cache, v_cache, k_scale=None, v_scale=None):
     """Decode step, one token per sequence: qkv [B, (H + 2*Hkv)*D] (the fused projection output) ->
     rotated q [B, H, D]; rotated k and v are written into the dense caches [Bc, Hkv, Lc, D] at the
-    device-side position ``pos_t`` ([1] int64). cos_row / sin_row: fp32 [1, D] rows at that position."""
+    device-side position ``pos_t`` ([1] int64). cos_row / sin_row: fp32 [1, D] rows at that position.
+    uint8 caches (int8 + 128) take ``k_scale`` / ``v_scale``, the [Hkv] fp32 quant scales (read on the device): the
+    value a cache of qkv's dtype would have received is stored as ``quantize_kv_int8`` of it."""
     B = qkv.shape[0]
+    quant = k_cache.dtype == torch.uint8
+    if quant != (v_cache.dtype == torch.uint8):
+        raise ValueError("decode_rope_cache: key and value cache must both be uint8 (int8 + 128) or both float")
+    if quant != (k_scale is not None) or quant != (v_scale is not None):
+        raise ValueError("decode_rope_cache: k_scale and v_scale ([kv_heads] quant scales) go with uint8 caches, "
+                         "and only with them")
+    if quant:
+        k_scale = k_scale.to(device=qkv.device, dtype=torch.float32).reshape(Hkv).contiguous()
+        v_scale = v_scale.to(device=qkv.device, dtype=torch.float32).reshape(Hkv).contiguous()
+        if (L.hip_enabled_for(qkv) and qkv.dtype in (torch.bfloat16, torch.float16) and D % 16 == 0
+                and qkv.stride(-1) == 1 and k_cache.is_contiguous() and v_cache.is_contiguous()
+                and L.has("pa_decode_rope_cache_q8")):
+            q = torch.empty(B, H, D, dtype=qkv.dtype, device=qkv.device)
+            cs = cos_row.float().contiguous()
+            sn = sin_row.float().contiguous()
+            L.call("pa_decode_rope_cache_q8", L.ptr(qkv), qkv.stride(0), L.ptr(cs), L.ptr(sn), L.ptr(pos_t),
+                   L.ptr(q), L.ptr(k_cache), L.ptr(v_cache), L.ptr(k_scale), L.ptr(v_scale), B, H, Hkv, D,
+                   k_cache.shape[2], L.dcode(qkv), L.stream_ptr())
+            return q
+        q, k, v = qkv.split([H * D, Hkv * D, Hkv * D], -1)
+        q = apply_rotary(q.reshape(B, 1, H, D), cos_row, sin_row)
+        k = apply_rotary(k.reshape(B, 1, Hkv, D), cos_row, sin_row)
+        k_cache[:B].index_copy_(2, pos_t, quantize_kv_int8(k, k_scale).transpose(1, 2))
+        v_cache[:B].index_copy_(2, pos_t, quantize_kv_int8(v.reshape(B, 1, Hkv, D), v_scale).transpose(1, 2))
+        return q.reshape(B, H, D)
     if (L.hip_enabled_for(qkv) and qkv.dtype in L._DT and D % 16 == 0 and qkv.stride(-1) == 1
             and k_cache.is_contiguous() and v_cache.is_contiguous() and L.has("pa_decode_rope_cache")):
         q = torch.empty(B, H, D, dtype=qkv.dtype, device=qkv.device)
