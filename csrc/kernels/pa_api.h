@@ -97,6 +97,16 @@ PA_EXPORT int pa_paged_decode_attn_q8(const void* q, const void* kc, const void*
                                       int Hkv, int D, int bs, int max_blocks, int splits, int64_t blk_stride,
                                       int64_t head_stride, float scale, hipStream_t st);
 
+// prefill_paged_attn.hip
+PA_EXPORT int pa_paged_prefill_attn(const void* q, const void* kc, const void* vc, const int* tables, const int* cu_q,
+                                    const int* ctx_lens, void* out, int B, int H, int Hkv, int D, int bs,
+                                    int max_blocks, int max_q, int64_t blk_stride, int64_t head_stride, float scale,
+                                    hipStream_t st);
+PA_EXPORT int pa_paged_prefill_attn_q8(const void* q, const void* kc, const void* vc, const float* k_dq,
+                                       const float* v_dq, const int* tables, const int* cu_q, const int* ctx_lens,
+                                       void* out, int B, int H, int Hkv, int D, int bs, int max_blocks, int max_q,
+                                       int64_t blk_stride, int64_t head_stride, float scale, hipStream_t st);
+
 // decode_fused.hip
 PA_EXPORT int pa_add_rms_norm_fwd(const void* x, const void* r, const void* w, void* s_out, void* y, int64_t rows,
                                   int64_t cols, float eps, int dtype, hipStream_t st);

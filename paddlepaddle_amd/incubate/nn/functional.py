@@ -658,8 +658,10 @@ def block_multihead_attention(qkv, key_cache, value_cache, seq_lens_encoder, seq
     pre_key_cache / pre_value_cache [B, kv_heads, P, D] (prefix caches): a prefilling sequence's cache positions
     0 .. P-1 receive them and its tokens start at P; its attention covers the prefix plus its tokens, causal
     (bottom-right) or through the additive ``mask`` [B, 1, S, P + S] when given; decode tokens with ``tgt_mask``
-    [B, 1, 1, L] add it over their cache positions. The masked / prefixed phases run a math path (per-sequence
-    lengths read on the host), the others the HIP kernels."""
+    [B, 1, 1, L] add it over their cache positions. A prefix-cache prefill without ``mask`` over a bf16 cache
+    (head_dim 128) runs the paged prefill kernel over the cache it has just filled (ops.paged_prefill_attention,
+    lengths on the device); the masked phases, and a prefix with a quantised cache or another dtype, run a math
+    path (per-sequence lengths read on the host), the others the HIP kernels."""
     if (pre_key_cache is None) != (pre_value_cache is None):
         raise ValueError("block_multihead_attention: pre_key_cache and pre_value_cache go together")
     quant_cache = cache_k_quant_scales is not None
@@ -764,7 +766,13 @@ def block_multihead_attention(qkv, key_cache, value_cache, seq_lens_encoder, seq
     run_decode = max_dec is None or max_dec > 0
     prefill_tok = enc[bid] > 0
     o = None
-    if run_prefill and (P or mask is not None):
+    if (run_prefill and P and mask is None and not quant_cache
+            and _ops.attention._prefill_hip_ok(q.to(adt), kc, vc, Hk)):
+        # prefix-cache prefill on the paged prefill kernel: prefix and tokens are in the cache by now. Decode rows
+        # ride along (one token over their own context) and are replaced by the decode kernel's result below.
+        ctx = dec + P * (enc > 0).long() + (cu[1:] - cu[:-1])
+        o = _ops.paged_prefill_attention(q.to(adt), kc, vc, bt, cu, ctx, max_q=max_enc if max_enc else None)
+    elif run_prefill and (P or mask is not None):
         o = _blha_prefill_math(q.to(adt), k.to(adt), v.to(adt), cu, enc, pk, pv, _t(mask))
     elif run_prefill:
         mq = max_enc if max_enc else T

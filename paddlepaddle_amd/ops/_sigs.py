@@ -66,6 +66,8 @@ SIGS = {
     "pa_paged_decode_attn": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32,
                              _i64, _i64, _f32, _vp],
     "pa_paged_decode_attn_q8": [_vp] * 12 + [_i32, _i32, _i32, _i32, _i32, _i32, _i32, _i64, _i64, _f32, _vp],
+    "pa_paged_prefill_attn": [_vp] * 7 + [_i32] * 7 + [_i64, _i64, _f32, _vp],
+    "pa_paged_prefill_attn_q8": [_vp] * 9 + [_i32] * 7 + [_i64, _i64, _f32, _vp],
     # gemm epilogue companions
     "pa_colsum": [_vp, _vp, _vp, _i64, _i64, _i32, _vp],
     "pa_dwconv_fwd": [_vp, _vp, _vp, _vp, _vp, _i32, _vp],

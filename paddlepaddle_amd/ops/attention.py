@@ -668,14 +668,126 @@ def dense_decode_attention(q, key_cache, value_cache, lens, scale=None, max_len=
             K, V = _dequant_gathered(key_cache[:N], value_cache[:N], lens, q8)
             return _decode_math(q, K, V, valid, scale)
         return _decode_math(q, key_cache, value_cache, valid, scale)
-    nb = Lc // _VBLK
-    key = (N, Hkv, nb, q.device)
+    tables = _dense_tables(N, Hkv, Lc // _VBLK, q.device)
+    ml = Lc if max_len is None else int(max_len)
+    return _decode_launch(q, key_cache, value_cache, tables, lens, Hkv, _VBLK, _VBLK * D, Lc * D, scale, ml, q8)
+
+
+def _dense_tables(N, Hkv, nb, device):
+    """Block tables [N, nb] that view a dense [N, Hkv, nb * 64, D] cache as virtual 64-token blocks."""
+    key = (N, Hkv, nb, device)
     tables = _DENSE_TABLES.get(key)
     if tables is None:  # identical for every layer / step: built once (also outside any captured graph)
-        tables = (torch.arange(N, device=q.device, dtype=torch.int32)[:, None] * (Hkv * nb)
-                  + torch.arange(nb, device=q.device, dtype=torch.int32)[None])
+        tables = (torch.arange(N, device=device, dtype=torch.int32)[:, None] * (Hkv * nb)
+                  + torch.arange(nb, device=device, dtype=torch.int32)[None])
         if len(_DENSE_TABLES) > 64:
             _DENSE_TABLES.clear()
         _DENSE_TABLES[key] = tables
-    ml = Lc if max_len is None else int(max_len)
-    return _decode_launch(q, key_cache, value_cache, tables, lens, Hkv, _VBLK, _VBLK * D, Lc * D, scale, ml, q8)
+    return tables
+
+
+def _prefill_math(q, K, V, cu, ctx, scale):
+    """fp32 chunk attention: q [T, H, D] packed by cu [B + 1]; K, V [B, Hkv, L, D] (each sequence's cache positions in
+    order); ctx [B]. Chunk token i of sequence b sees positions 0 .. max(ctx[b] - n_b, 0) + i that are below ctx[b];
+    rows cu does not cover see nothing and give zeros. Masked slots never reach the result (``_decode_math``)."""
+    T, B, Lk = q.shape[0], ctx.numel(), K.shape[2]
+    cu, ctx = cu.long(), ctx.long()
+    tok = torch.arange(T, device=q.device)
+    bid = torch.searchsorted(cu[1:].contiguous(), tok, right=True)
+    covered = (tok >= cu[0]) & (bid < B)
+    bid = bid.clamp(max=B - 1)
+    start = (ctx - (cu[1:] - cu[:-1])).clamp(min=0)
+    lim = start[bid] + tok - cu[bid]
+    pos = torch.arange(Lk, device=q.device)[None]
+    valid = (pos <= lim[:, None]) & (pos < ctx[bid][:, None]) & covered[:, None]
+    return _decode_math(q, K[bid], V[bid], valid, scale)
+
+
+def _prefill_args(q, key_cache, value_cache, cu_seqlens_q, ctx_lens, k_dequant, v_dequant):
+    """Shared checks of the prefill wrappers: (Hkv, q8 scales or None)."""
+    T, H, D = q.shape
+    Hkv = key_cache.shape[1]
+    if Hkv < 1 or H % Hkv != 0:
+        raise ValueError(f"prefill attention: {H} query heads are not a multiple of {Hkv} kv heads")
+    if cu_seqlens_q.numel() != ctx_lens.numel() + 1:
+        raise ValueError(f"prefill attention: cu_seqlens_q holds {cu_seqlens_q.numel()} entries for "
+                         f"{ctx_lens.numel()} sequences (want one more)")
+    q8 = _q8_args(q, key_cache, value_cache, Hkv, k_dequant, v_dequant, None, None)
+    return Hkv, q8
+
+
+def _prefill_launch(q, kc, vc, tables, cu, ctx, Hkv, bs, blk_stride, head_stride, scale, max_q, q8):
+    T, H, D = q.shape
+    q = q.contiguous()
+    tables = tables.to(torch.int32).contiguous()
+    cu32 = cu.to(device=q.device, dtype=torch.int32).contiguous()
+    ctx32 = ctx.to(device=q.device, dtype=torch.int32).contiguous()
+    B = ctx32.numel()
+    out = torch.zeros_like(q)  # rows cu does not cover, and empty chunks, stay zero
+    mq = T if max_q is None else min(int(max_q), T)
+    if q8 is not None:
+        L.call("pa_paged_prefill_attn_q8", L.ptr(q), L.ptr(kc), L.ptr(vc), L.ptr(q8[0]), L.ptr(q8[1]), L.ptr(tables),
+               L.ptr(cu32), L.ptr(ctx32), L.ptr(out), B, H, Hkv, D, bs, tables.shape[1], mq, int(blk_stride),
+               int(head_stride), float(scale), L.stream_ptr())
+        return out
+    L.call("pa_paged_prefill_attn", L.ptr(q), L.ptr(kc), L.ptr(vc), L.ptr(tables), L.ptr(cu32), L.ptr(ctx32),
+           L.ptr(out), B, H, Hkv, D, bs, tables.shape[1], mq, int(blk_stride), int(head_stride), float(scale),
+           L.stream_ptr())
+    return out
+
+
+def _prefill_hip_ok(q, key_cache, value_cache, Hkv):
+    name = "pa_paged_prefill_attn_q8" if key_cache.dtype == torch.uint8 else "pa_paged_prefill_attn"
+    T, H, D = q.shape
+    return (L.hip_enabled_for(q) and L.has(name) and q.dtype == torch.bfloat16
+            and key_cache.dtype in (torch.bfloat16, torch.uint8) and value_cache.dtype == key_cache.dtype
+            and D == 128 and H // Hkv in (1, 2, 4, 8) and key_cache.is_contiguous() and value_cache.is_contiguous())
+
+
+@static_op
+def paged_prefill_attention(q, key_cache, value_cache, block_tables, cu_seqlens_q, ctx_lens, scale=None, max_q=None,
+                            k_dequant=None, v_dequant=None):
+    """Attention of a chunk of new tokens per sequence over a paged KV cache that already holds the chunk (chunked
+    prefill, prefix-cache prefill, speculative verify). q [T, H, D], the step's tokens packed per sequence by
+    cu_seqlens_q [B + 1]; caches [num_blocks, Hkv, block_size, D]; block_tables [B, max_blocks]; ctx_lens [B]: the
+    cache positions the last chunk token of a sequence sees. With n_b tokens in the chunk and start_b =
+    max(ctx_lens[b] - n_b, 0), chunk token i attends to positions 0 .. start_b + i (causal, bottom-right aligned per
+    sequence). Returns [T, H, D]; rows cu_seqlens_q does not cover are zero.
+    HIP MFMA kernel (csrc/kernels/prefill_paged_attn.hip) for bf16 q, head_dim 128, bf16 or uint8 caches and H / Hkv
+    in {1, 2, 4, 8}; the lengths are read on the device. ``max_q`` bounds n_b (host hint for the grid; defaults to T).
+    uint8 caches (int8 + 128) need ``k_dequant`` / ``v_dequant`` as for paged_decode_attention; the chunk is read back
+    quantised. Anything else runs an fp32 fallback that gathers only the blocks the tables name."""
+    T, H, D = q.shape
+    _, _, bs, _ = key_cache.shape
+    scale = 1.0 / math.sqrt(D) if scale is None else float(scale)
+    Hkv, q8 = _prefill_args(q, key_cache, value_cache, cu_seqlens_q, ctx_lens, k_dequant, v_dequant)
+    if _prefill_hip_ok(q, key_cache, value_cache, Hkv):
+        return _prefill_launch(q, key_cache, value_cache, block_tables, cu_seqlens_q, ctx_lens, Hkv, bs,
+                               Hkv * bs * D, bs * D, scale, max_q, q8)
+    B, nblk = block_tables.shape
+    tab = block_tables.long()
+    K = key_cache[tab].permute(0, 2, 1, 3, 4).reshape(B, Hkv, nblk * bs, D)
+    V = value_cache[tab].permute(0, 2, 1, 3, 4).reshape(B, Hkv, nblk * bs, D)
+    if q8 is not None:
+        K, V = _dequant_gathered(K, V, ctx_lens, q8)
+    return _prefill_math(q, K, V, cu_seqlens_q.to(q.device), ctx_lens.to(q.device), scale)
+
+
+@static_op
+def dense_prefill_attention(q, key_cache, value_cache, cu_seqlens_q, ctx_lens, scale=None, max_q=None,
+                            k_dequant=None, v_dequant=None):
+    """paged_prefill_attention over a dense per-sequence cache [B, Hkv, Lc, D]: the same HIP kernel streams it as
+    virtual 64-token blocks (Lc % 64 == 0, the block tables of dense_decode_attention)."""
+    T, H, D = q.shape
+    _, _, Lc, _ = key_cache.shape
+    B = ctx_lens.numel()
+    scale = 1.0 / math.sqrt(D) if scale is None else float(scale)
+    Hkv, q8 = _prefill_args(q, key_cache, value_cache, cu_seqlens_q, ctx_lens, k_dequant, v_dequant)
+    if not _prefill_hip_ok(q, key_cache, value_cache, Hkv) or Lc % _VBLK != 0:
+        K, V = key_cache[:B], value_cache[:B]
+        if q8 is not None:
+            K, V = _dequant_gathered(K, V, ctx_lens, q8)
+        return _prefill_math(q, K, V, cu_seqlens_q.to(q.device), ctx_lens.to(q.device), scale)
+    tables = _dense_tables(B, Hkv, Lc // _VBLK, q.device)
+    return _prefill_launch(q, key_cache, value_cache, tables, cu_seqlens_q, ctx_lens, Hkv, _VBLK, _VBLK * D, Lc * D,
+                           scale, max_q, q8)

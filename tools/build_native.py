@@ -32,6 +32,8 @@ PA_API = os.path.join(KERNELS, "pa_api.h")  # the C API of _C_hip.so, included b
 
 HIP_FLAGS = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-munsafe-fp-atomics",
              "-Wno-unused-result", "-Wno-unused-variable"]
+# per-file additions: new kernels are compiled without packed fp32 VALU ops (v_pk_add / mul / fma_f32)
+HIP_FILE_FLAGS = {"prefill_paged_attn.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
 
 
 def _newer(src_list, out):
@@ -63,7 +65,8 @@ def build_hip(verbose=False, jobs=None):
             todo.append((s, o))
     jobs = jobs or min(8, max(1, os.cpu_count() or 1))
     with cf.ThreadPoolExecutor(jobs) as ex:
-        futs = [ex.submit(_run, [hipcc, *HIP_FLAGS, "-c", s, "-o", o]) for s, o in todo]
+        futs = [ex.submit(_run, [hipcc, *HIP_FLAGS, *HIP_FILE_FLAGS.get(os.path.basename(s), []), "-c", s, "-o", o])
+                for s, o in todo]
         for f in futs:
             f.result()
     out = os.path.join(PKG, "_C_hip.so")
