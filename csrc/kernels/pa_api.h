@@ -265,6 +265,16 @@ PA_EXPORT int64_t pa_colsum_nparts(int64_t rows);
 PA_EXPORT int pa_fold_partials(const float* ws, void* out, int64_t cols, int64_t nparts, int dtype_acc,
                                hipStream_t st);
 
+// mx.hip
+PA_EXPORT int pa_mx_quant(const void* x, void* q, void* scales, int64_t R, int64_t K, int in_dtype, int fmt,
+                          hipStream_t st);
+PA_EXPORT int pa_gemm_mx(const void* a, const void* sa, const void* b, const void* sb, void* c, const float* bias,
+                         int64_t M, int64_t N, int64_t K, int fmt_a, int out, hipStream_t st);
+PA_EXPORT int pa_gemm_mx_small_m_splits(int64_t M, int64_t N, int64_t K);
+PA_EXPORT int pa_gemm_mx_small_m(const void* a, const void* sa, const void* b, const void* sb, void* c,
+                                 const float* bias, float* ws, int M, int N, int K, int fmt_a, int out, int splits,
+                                 hipStream_t st);
+
 // norm.hip
 PA_EXPORT int pa_rms_norm_fwd(const void* x, const void* w, void* y, float* rstd, int64_t rows, int64_t cols,
                               float eps, int dtype, hipStream_t st);

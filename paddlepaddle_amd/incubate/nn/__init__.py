@@ -79,6 +79,49 @@ class FP8Linear(_nn.Layer):
                 f"dtype={self._dtype}")
 
 
+class MXFP4Linear(_nn.Layer):
+    """Inference nn.Linear with an OCP MXFP4 weight (F.mx_linear): the weight is kept as the buffers ``w_q`` (uint8
+    [out, in32 / 2], two e2m1 codes per byte, K-major) and ``w_s`` (uint8 [out, in32 / 32], E8M0 block scales), in32 =
+    ``in`` rounded up to a multiple of 32; both travel with state_dict. ``act_format``: the format activations are
+    quantised to on the way in, "mxfp8" or "mxfp4". No backward. Reference: none in Paddle 3.0; the project's own
+    name."""
+
+    def __init__(self, in_features, out_features, bias_attr=None, act_format="mxfp8", name=None, _weight=None,
+                 _bias=None):
+        super().__init__()
+        import torch
+        from ...framework.tensor import _wrap
+        from ...ops import mx as _mx
+        _mx._check_fmt(act_format)
+        self._in_features, self._out_features, self.act_format, self.name = in_features, out_features, act_format, name
+        k32 = -(-in_features // 32) * 32
+        if _weight is None:  # an empty layer to load a state_dict into
+            w_q, w_s = torch.zeros(out_features, k32 // 2, dtype=torch.uint8), torch.full(
+                (out_features, k32 // 32), 127, dtype=torch.uint8)
+        else:
+            w_q, w_s = _mx.quantize_weight(_weight)
+        self.register_buffer("w_q", _wrap(w_q))
+        self.register_buffer("w_s", _wrap(w_s))
+        if _weight is None:
+            self.bias = None if bias_attr is False else self.create_parameter([out_features], attr=bias_attr,
+                                                                             is_bias=True)
+        else:
+            self.bias = _bias
+
+    @classmethod
+    def from_linear(cls, layer, act_format="mxfp8"):
+        """An MXFP4Linear of an existing nn.Linear: its [in, out] weight is quantised once, on the device it is on, to
+        the K-major image; the bias is shared."""
+        k, n = layer.weight.shape
+        return cls(k, n, act_format=act_format, _weight=layer.weight._t, _bias=layer.bias)
+
+    def forward(self, x):
+        return F.mx_linear(x, self.w_q, self.w_s, self.bias, self.act_format)
+
+    def extra_repr(self):
+        return f"in_features={self._in_features}, out_features={self._out_features}, act_format={self.act_format}"
+
+
 class FusedDropoutAdd(_nn.Layer):
     def __init__(self, p=0.5, mode="upscale_in_train", name=None):
         super().__init__()

@@ -248,6 +248,26 @@ def fp8_linear(x, weight, bias=None, state=None):
     return _wrap(_f8.fp8_linear(xt, _t(weight), _t(bias), state, emulate=not xt.is_cuda))
 
 
+def mx_quantize(x, format="mxfp4"):
+    """OCP Microscaling quantization along the last dimension (a multiple of 32) in blocks of 32: returns (q, scales)
+    with scales uint8 [rows, K / 32] (E8M0: 2^(e - 127)) and q uint8 [rows, K / 2] for "mxfp4" (e2m1, element 2i in
+    the low nibble of byte i) or float8_e4m3fn [rows, K] for "mxfp8"; the rule is in ops/mx.py. On the device one HIP
+    pass (csrc/kernels/mx.hip). Reference: none in Paddle 3.0; this name is the project's own."""
+    from ...ops import mx as _mx
+    q, s = _mx.quantize_mx(_t(x), format)
+    return _wrap(q), _wrap(s)
+
+
+def mx_linear(x, w_q, w_s, bias=None, act_format="mxfp8"):
+    """y = x @ W + bias for an mxfp4 weight stored K-major (w_q [out, in / 2], w_s [out, in / 32]: mx_quantize of the
+    transposed weight, or MXFP4Linear's buffers): x is quantised to ``act_format`` ("mxfp8" / "mxfp4") on the device and
+    the product runs on the block-scaled MFMA. Inference only: a tensor that requires grad is an error unless gradients
+    are disabled. Shapes the kernels do not take (in % 128, out % 4) multiply the dequantised operands with the bf16
+    linear and count in ops.mx.CALLS["fallback"]. Reference: none in Paddle 3.0; the project's own name."""
+    from ...ops import mx as _mx
+    return _wrap(_mx.mx_linear(_t(x), _t(w_q), _t(w_s), _t(bias), act_format))
+
+
 def fused_linear_activation(x, y, bias, trans_x=False, trans_y=False, activation=None):
     act = {None: None, "none": None, "gelu": "gelu", "relu": "relu"}[activation]
     xt, w = _t(x), _t(y)

@@ -106,6 +106,11 @@ SIGS = {
     "pa_wo_gemm": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp],
     "pa_wo_gemm_splits": [_i64, _i64, _i64, _i32],
     "pa_wo_dequant": [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp],
+    # MX (block-scaled fp4 / fp8) quantiser and GEMMs (csrc/kernels/mx.hip)
+    "pa_mx_quant": [_vp, _vp, _vp, _i64, _i64, _i32, _i32, _vp],
+    "pa_gemm_mx": [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i32, _i32, _vp],
+    "pa_gemm_mx_small_m_splits": [_i64, _i64, _i64],
+    "pa_gemm_mx_small_m": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp],
     "pa_gemm_skinny_ok": [_i64, _i64],
     "pa_gemm_skinny_stats_chunks": [_i64, _i64, _i64],
     "pa_gemm_skinny_stats": [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _i32, _vp, _vp],

@@ -33,7 +33,8 @@ PA_API = os.path.join(KERNELS, "pa_api.h")  # the C API of _C_hip.so, included b
 HIP_FLAGS = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-munsafe-fp-atomics",
              "-Wno-unused-result", "-Wno-unused-variable"]
 # per-file additions: new kernels are compiled without packed fp32 VALU ops (v_pk_add / mul / fma_f32)
-HIP_FILE_FLAGS = {"prefill_paged_attn.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
+_NO_PK_F32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
+HIP_FILE_FLAGS = {"prefill_paged_attn.hip": _NO_PK_F32, "mx.hip": _NO_PK_F32}
 
 
 def _newer(src_list, out):
