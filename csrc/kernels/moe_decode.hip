@@ -1,0 +1,363 @@
+// MoE decode: the SwiGLU expert FFN of fused_moe for at most 64 tokens (serving), as four launches with no host
+// synchronisation: plan -> up projection (+ SwiGLU) -> down projection (K split) -> combine.
+// Reference behaviour: python/paddle/incubate/nn/functional/fused_moe.py:20 (softmax gate, top-k, optional
+// renormalisation, ffn1 [E, d, 2f] -> swiglu -> ffn2 [E, f, d], weighted sum over the token's experts).
+//
+// Decode MoE is bound by the bytes of the routed experts' weights, so the two projections are built like the dense
+// decode GEMM (gemm.hip gemm_small_m_kernel): few rows, a 4-deep LDS ring filled by LDS-DMA, one barrier per K
+// tile, counted vmcnt waits. What is this file's own:
+//   * moe_decode_plan_k, one workgroup: softmax + top-k + renormalisation per token (one wave per token), then a
+//     stable counting sort of the T * topk entries held in LDS. A token picks an expert at most once, so an expert
+//     holds at most T <= 64 rows = one M tile: the ascending list of non-empty experts IS the tile map, and the
+//     GEMM grids are (column bands) x (slots), a slot past the active count exiting at once.
+//   * the row-gather stage: the A operand of the up projection is not a gathered copy of x; the token index
+//     perm[row] / topk goes into the per-lane LDS-DMA source address. Rows past the expert's count are clamped
+//     reads that are never stored.
+//   * the up projection stages the value band [n0, n0 + 64) and the gate band [f + n0, f + n0 + 64) of w1[e] side
+//     by side, so bias + silu(value) * gate happens on the accumulators and h [n, f] is written once, in bf16.
+//   * the down projection splits K over gridDim.z into fp32 slabs [split][n][d]; every row of every slab is
+//     written (each sorted row belongs to exactly one expert), so there is no memset and no atomic.
+//   * moe_decode_combine_k sums slabs, bias and the token's experts in a fixed ascending order: bit-identical
+//     from run to run.
+#include "launch.h"
+#include "mfma_tile.h"
+
+namespace pa {
+namespace {
+
+constexpr int kMdBK = 64, kMdBN = 64, kMdNW = 4, kMdStages = 4;
+constexpr int kMdMaxT = 64, kMdMaxE = 256, kMdMaxTopk = 8, kMdMaxN = kMdMaxT * kMdMaxTopk;
+
+// ------------------------------------------------------------------------------------------------ plan
+// logits [T, E] -> val / idx [T, topk], offs [E + 1], perm [n] (sorted row -> entry, stable), pos [n] (entry ->
+// sorted row), active [min(E, n)] (non-empty experts ascending, -1 behind them), n_active [1].  n = T * topk.
+template <class TL>
+__global__ __launch_bounds__(256) void moe_decode_plan_k(const TL* __restrict__ logits, int T, int E, int topk,
+                                                         int norm, float* __restrict__ val, int* __restrict__ idx,
+                                                         int* __restrict__ offs, int* __restrict__ perm,
+                                                         int* __restrict__ pos, int* __restrict__ active,
+                                                         int* __restrict__ n_active) {
+  __shared__ float s_val[kMdMaxN];
+  __shared__ int s_idx[kMdMaxN], s_rank[kMdMaxN], s_offs[kMdMaxE], s_wtot[4];
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const int n = T * topk;
+
+  // gate: lane holds experts lane, lane + 64, lane + 128, lane + 192
+  for (int t = wave; t < T; t += 4) {
+    float p[4];
+    float mx = -INFINITY;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int c = lane + 64 * i;
+      p[i] = c < E ? to_f(logits[(int64_t)t * E + c]) : -INFINITY;
+      mx = fmaxf(mx, p[i]);
+    }
+    mx = wave_max(mx);
+    float sum = 0.f;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      p[i] = lane + 64 * i < E ? expf(p[i] - mx) : 0.f;
+      sum += p[i];
+    }
+    sum = wave_sum(sum);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      p[i] = p[i] / sum;
+      if (!(p[i] >= 0.f)) p[i] = 0.f;           // NaN logits: still topk distinct experts
+      if (lane + 64 * i >= E) p[i] = -2.f;      // never picked: topk <= E
+    }
+    // topk rounds of (largest value, lowest index); a picked expert drops to -1
+    float tot = 0.f, myv = 0.f;
+    int myi = 0;
+    for (int j = 0; j < topk; ++j) {
+      float bv = -3.f;
+      int bi = 0x7fffffff;
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+        if (p[i] > bv) { bv = p[i]; bi = lane + 64 * i; }
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) {
+        const float ov = __shfl_xor(bv, o, 64);
+        const int oi = __shfl_xor(bi, o, 64);
+        if (ov > bv || (ov == bv && oi < bi)) { bv = ov; bi = oi; }
+      }
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+        if (lane + 64 * i == bi) p[i] = -1.f;
+      if (lane == j) { myv = bv; myi = bi; }
+      tot += bv;
+    }
+    if (lane < topk) {
+      s_val[t * topk + lane] = norm ? myv / tot : myv;
+      s_idx[t * topk + lane] = myi;
+    }
+  }
+  __syncthreads();
+
+  // stable counting sort: thread e walks the entries in order and numbers its own
+  int c = 0;
+  if (tid < E)
+    for (int j = 0; j < n; ++j)
+      if (s_idx[j] == tid) s_rank[j] = c++;
+  // one exclusive scan for both the row offsets (low half) and the active-list slots (high half); n <= 512
+  const int v = c | ((c > 0) << 16);
+  int inc = v;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const int u = __shfl_up(inc, o, 64);
+    if (lane >= o) inc += u;
+  }
+  if (lane == 63) s_wtot[wave] = inc;
+  __syncthreads();
+  int base = 0, total = 0;
+#pragma unroll
+  for (int w = 0; w < 4; ++w) {
+    if (w < wave) base += s_wtot[w];
+    total += s_wtot[w];
+  }
+  const int exc = base + inc - v;
+  const int n_act = total >> 16, slots = E < n ? E : n;
+  if (tid < E) {
+    s_offs[tid] = exc & 0xffff;
+    offs[tid] = exc & 0xffff;
+    if (c > 0) active[exc >> 16] = tid;
+  }
+  if (tid >= n_act && tid < slots) active[tid] = -1;
+  if (tid == 0) {
+    offs[E] = total & 0xffff;
+    *n_active = n_act;
+  }
+  __syncthreads();
+  for (int i = tid; i < n; i += 256) {
+    const int e = s_idx[i];
+    const int r = s_offs[e] + s_rank[i];
+    pos[i] = r;
+    perm[r] = i;
+    val[i] = s_val[i];
+    idx[i] = e;
+  }
+}
+
+// ------------------------------------------------------------------------------------------------ FFN
+struct MoeDecArgs {
+  const uint16_t *x, *w1, *w2, *b1, *b2;
+  const float* val;
+  const int *idx, *offs, *perm, *pos, *active, *n_active;
+  uint16_t* h;    // [n, f] bf16, sorted row order
+  float* ws;      // [splits, n, d] fp32
+  uint16_t* out;  // [T, d] bf16
+  int T, E, topk, d, f, n, k_per, splits;
+};
+
+__device__ __forceinline__ float silu(float a) { return a / (1.f + __expf(-a)); }
+
+// One tile of one active expert: C[rows of e (<= MT * 16), 64 columns] over nk K tiles.
+//   UP:  A = x gathered through perm, B = the value and the gate band of w1[e]; epilogue bias + swiglu -> h (bf16)
+//   !UP: A = rows of h,              B = one band of w2[e], K range of split blockIdx.z;   epilogue fp32 slab
+// 4 waves, wave w owns columns [16 w, 16 w + 16) of the band(s) for all MT row fragments. Ring of kMdStages stages of
+// A ([AR][64] K-major, swizzled) + NB B images ([64 k][64] MN-major): 20-24 KiB a stage for UP, 12-16 KiB for down.
+template <int MT, bool UP>
+__device__ __forceinline__ void moe_decode_tile(const MoeDecArgs& p) {
+  constexpr int AR = MT <= 2 ? 32 : 64;  // staged A rows: one or two 1-KiB LDS-DMA instructions per thread
+  constexpr int NQA = AR / (8 * kMdNW), NB = UP ? 2 : 1;
+  constexpr int A_BYTES = AR * kMdBK * 2, B_BYTES = kMdBN * kMdBK * 2, STAGE = A_BYTES + NB * B_BYTES;
+  constexpr int NL = NQA + NB * (kMdBN / (8 * kMdNW));  // glds per thread per K tile
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const int slot = blockIdx.y;
+  if (slot >= *p.n_active) return;
+  const int e = p.active[slot];
+  if ((unsigned)e >= (unsigned)p.E) return;
+  const int r0 = p.offs[e];
+  const int cnt = min(min(p.offs[e + 1] - r0, MT * 16), p.n - r0);
+  if (r0 < 0 || cnt <= 0) return;
+  const int n0 = blockIdx.x * kMdBN;
+  const int K = UP ? p.d : p.f, ldb = UP ? 2 * p.f : p.d;
+  const int kbeg = UP ? 0 : blockIdx.z * p.k_per;
+  const int nk = (UP ? p.d : p.k_per) / kMdBK;
+  const uint16_t* bw = (UP ? p.w1 : p.w2) + (int64_t)e * p.d * p.f * (UP ? 2 : 1);
+
+  // row-gather stage: the source row of every image row this lane fills, swizzled chunk included
+  const uint16_t* arow[NQA];
+#pragma unroll
+  for (int i = 0; i < NQA; ++i) {
+    const int row = (i * kMdNW + wave) * 8 + (lane >> 3);
+    const int lc = (lane & 7) ^ k_swz(row);
+    const int rr = r0 + min(row, cnt - 1);
+    int src = rr;
+    if (UP) src = min(max(p.perm[rr] / p.topk, 0), p.T - 1);
+    arow[i] = (UP ? p.x : p.h) + (int64_t)src * K + kbeg + lc * 8;
+  }
+  auto stage_tile = [&](int t) {
+    char* base = smem + (t % kMdStages) * STAGE;
+#pragma unroll
+    for (int i = 0; i < NQA; ++i) glds16(arow[i] + t * kMdBK, base + (i * kMdNW + wave) * 1024);
+    stage<kMdBN, false, kMdNW>(bw, ldb, n0, ldb, kbeg + t * kMdBK, base + A_BYTES, wave, lane);
+    if (UP) stage<kMdBN, false, kMdNW>(bw, ldb, p.f + n0, ldb, t * kMdBK, base + A_BYTES + B_BYTES, wave, lane);
+  };
+
+  f32x4 acc[MT][NB];
+#pragma unroll
+  for (int i = 0; i < MT; ++i)
+#pragma unroll
+    for (int j = 0; j < NB; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+  const int pro = min(kMdStages - 1, nk);
+  for (int t = 0; t < pro; ++t) stage_tile(t);
+  // wait for tile 0: (pro - 1) tiles may stay in flight
+  if (pro >= 3) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * NL) : "memory");
+  else if (pro == 2) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NL) : "memory");
+  else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  bar();
+
+#pragma unroll 1
+  for (int t = 0; t < nk; ++t) {
+    if (t + kMdStages - 1 < nk) stage_tile(t + kMdStages - 1);
+    const char* aimg = smem + (t % kMdStages) * STAGE;
+    const char* bimg = aimg + A_BYTES;
+#pragma unroll
+    for (int s = 0; s < 2; ++s) {
+      bf16x8_t bf[NB];
+#pragma unroll
+      for (int j = 0; j < NB; ++j) bf[j] = frag<kMdBN, false>(bimg + j * B_BYTES, wave * 16, s, lane);
+#pragma unroll
+      for (int i = 0; i < MT; ++i) {
+        const bf16x8_t af = frag<AR, true>(aimg, i * 16, s, lane);
+#pragma unroll
+        for (int j = 0; j < NB; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bf[j], af, acc[i][j], 0, 0, 0);
+      }
+    }
+    // retire tile t + 1 (tiles issued after it may stay in flight)
+    const int after = min(nk - 1, t + kMdStages - 1) - (t + 1);
+    if (after >= 2) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * NL) : "memory");
+    else if (after == 1) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NL) : "memory");
+    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    bar();
+  }
+
+  // lane holds C[m = 16 i + (lane & 15)][n0 + 16 wave + 4 (lane >> 4) + 0..3]
+  const int col = n0 + wave * 16 + 4 * (lane >> 4);
+#pragma unroll
+  for (int i = 0; i < MT; ++i) {
+    const int m = i * 16 + (lane & 15);
+    if (m >= cnt) continue;
+    if constexpr (UP) {
+      float a[4] = {acc[i][0][0], acc[i][0][1], acc[i][0][2], acc[i][0][3]};
+      float g[4] = {acc[i][1][0], acc[i][1][1], acc[i][1][2], acc[i][1][3]};
+      if (p.b1) {
+        float ba[4], bg[4];
+        load4_16(p.b1 + (int64_t)e * 2 * p.f + col, ba);
+        load4_16(p.b1 + (int64_t)e * 2 * p.f + p.f + col, bg);
+#pragma unroll
+        for (int q = 0; q < 4; ++q) { a[q] += ba[q]; g[q] += bg[q]; }
+      }
+      *reinterpret_cast<uint2*>(p.h + (int64_t)(r0 + m) * p.f + col) =
+          make_uint2(pack_bf16(silu(a[0]) * g[0], silu(a[1]) * g[1]), pack_bf16(silu(a[2]) * g[2], silu(a[3]) * g[3]));
+    } else {
+      *reinterpret_cast<float4*>(p.ws + ((int64_t)blockIdx.z * p.n + r0 + m) * p.d + col) =
+          make_float4(acc[i][0][0], acc[i][0][1], acc[i][0][2], acc[i][0][3]);
+    }
+  }
+}
+
+template <int MT>
+__global__ __launch_bounds__(kMdNW * 64) void moe_decode_up_k(MoeDecArgs p) { moe_decode_tile<MT, true>(p); }
+template <int MT>
+__global__ __launch_bounds__(kMdNW * 64) void moe_decode_down_k(MoeDecArgs p) { moe_decode_tile<MT, false>(p); }
+
+template <int MT, bool UP>
+constexpr int moe_decode_smem() {
+  return kMdStages * ((MT <= 2 ? 32 : 64) * kMdBK * 2 + (UP ? 2 : 1) * kMdBN * kMdBK * 2);
+}
+
+// out[t][c] = sum_j val[t, j] * (sum_s slab[s][pos[t topk + j]][c] + b2[idx[t, j]][c]), j and s ascending
+__global__ __launch_bounds__(256) void moe_decode_combine_k(MoeDecArgs p) {
+  const int t = blockIdx.y;
+  const int c = (blockIdx.x * 256 + threadIdx.x) * 4;
+  if (c >= p.d) return;
+  float o[4] = {0.f, 0.f, 0.f, 0.f};
+  for (int j = 0; j < p.topk; ++j) {
+    const int ent = t * p.topk + j;
+    const int row = min(max(p.pos[ent], 0), p.n - 1);
+    float4 s = *reinterpret_cast<const float4*>(p.ws + (int64_t)row * p.d + c);
+    for (int sp = 1; sp < p.splits; ++sp) {
+      const float4 u = *reinterpret_cast<const float4*>(p.ws + ((int64_t)sp * p.n + row) * p.d + c);
+      s.x += u.x; s.y += u.y; s.z += u.z; s.w += u.w;
+    }
+    if (p.b2) {
+      float b[4];
+      const int e = min(max(p.idx[ent], 0), p.E - 1);
+      load4_16(p.b2 + (int64_t)e * p.d + c, b);
+      s.x += b[0]; s.y += b[1]; s.z += b[2]; s.w += b[3];
+    }
+    const float w = p.val[ent];
+    o[0] += w * s.x; o[1] += w * s.y; o[2] += w * s.z; o[3] += w * s.w;
+  }
+  *reinterpret_cast<uint2*>(p.out + (int64_t)t * p.d + c) = make_uint2(pack_bf16(o[0], o[1]), pack_bf16(o[2], o[3]));
+}
+
+bool moe_decode_shape_ok(int T, int E, int topk, int d, int f) {
+  return T >= 1 && T <= kMdMaxT && E >= 1 && E <= kMdMaxE && topk >= 1 && topk <= kMdMaxTopk && topk <= E &&
+         d >= kMdBK && f >= kMdBK && d % 64 == 0 && f % 64 == 0;
+}
+
+}  // namespace
+}  // namespace pa
+
+using namespace pa;
+
+// Gate + routing of a decode step: logits [T, E] (dtype 0 = fp32, 2 = bf16), T <= 64, E <= 256, topk <= min(8, E).
+PA_EXPORT int pa_moe_decode_plan(const void* logits, int dtype, int T, int E, int topk, int norm, float* val, int* idx,
+                                 int* offs, int* perm, int* pos, int* active, int* n_active, hipStream_t st) {
+  if (T < 1 || T > kMdMaxT || E < 1 || E > kMdMaxE || topk < 1 || topk > kMdMaxTopk || topk > E) return 1;
+  if (dtype == kF32)
+    hipLaunchKernelGGL(moe_decode_plan_k<float>, dim3(1), dim3(256), 0, st, (const float*)logits, T, E, topk, norm,
+                       val, idx, offs, perm, pos, active, n_active);
+  else if (dtype == kBF16)
+    hipLaunchKernelGGL(moe_decode_plan_k<bf16>, dim3(1), dim3(256), 0, st, (const bf16*)logits, T, E, topk, norm, val,
+                       idx, offs, perm, pos, active, n_active);
+  else
+    return 2;
+  return (int)hipGetLastError();
+}
+
+// K splits of the down projection the FFN runs with by default: the smallest divisor of f / 64 (at most 8, at least
+// 8 K tiles a split) that gives every compute unit two workgroups if all min(E, n) slots are active.
+PA_EXPORT int pa_moe_decode_splits(int n, int E, int d, int f) {
+  if (n < 1 || E < 1 || d < 64 || f < 64) return 1;
+  const int64_t wgs = (int64_t)(d / kMdBN) * (E < n ? E : n), target = 2 * device_cus();
+  const int tiles = f / kMdBK;
+  int s = 1;
+  for (int c = 1; c <= 8 && tiles / c >= 8; ++c) {
+    if (tiles % c) continue;
+    s = c;
+    if (wgs * c >= target) break;
+  }
+  return s;
+}
+
+// The expert FFN on a plan of pa_moe_decode_plan: x [T, d], w1 [E, d, 2f], w2 [E, f, d], b1 [E, 2f] / b2 [E, d] or
+// null, all bf16 and contiguous; h = n * f bf16 and ws = splits * n * d fp32 of workspace (n = T * topk, neither needs
+// clearing); out [T, d] bf16. d % 64 == 0, f % 64 == 0, (f / 64) % splits == 0.
+PA_EXPORT int pa_moe_decode_ffn(const void* x, const void* w1, const void* w2, const void* b1, const void* b2,
+                                const float* val, const int* idx, const int* offs, const int* perm, const int* pos,
+                                const int* active, const int* n_active, void* h, float* ws, void* out, int T, int E,
+                                int topk, int d, int f, int splits, hipStream_t st) {
+  if (!moe_decode_shape_ok(T, E, topk, d, f)) return 1;
+  if (splits < 1 || (f / kMdBK) % splits != 0) return 2;
+  MoeDecArgs p{(const uint16_t*)x, (const uint16_t*)w1, (const uint16_t*)w2, (const uint16_t*)b1, (const uint16_t*)b2,
+               val, idx, offs, perm, pos, active, n_active, (uint16_t*)h, ws, (uint16_t*)out,
+               T, E, topk, d, f, T * topk, f / splits, splits};
+  const int slots = E < p.n ? E : p.n;
+  const dim3 block(kMdNW * 64), gup(f / kMdBN, slots), gdn(d / kMdBN, slots, splits);
+  const auto run = [&](auto mt) {
+    constexpr int MT = decltype(mt)::value;
+    const int rc = launch_lds<moe_decode_up_k<MT>>(gup, block, moe_decode_smem<MT, true>(), st, p);
+    return rc ? rc : launch_lds<moe_decode_down_k<MT>>(gdn, block, moe_decode_smem<MT, false>(), st, p);
+  };
+  const int mt = (T + 15) / 16;
+  const int rc = mt == 1 ? run(IntC<1>{}) : mt == 2 ? run(IntC<2>{}) : mt == 3 ? run(IntC<3>{}) : run(IntC<4>{});
+  if (rc) return rc;
+  hipLaunchKernelGGL(moe_decode_combine_k, dim3((d / 4 + 255) / 256, T), dim3(256), 0, st, p);
+  return (int)hipGetLastError();
+}

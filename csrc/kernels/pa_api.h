@@ -265,6 +265,15 @@ PA_EXPORT int64_t pa_colsum_nparts(int64_t rows);
 PA_EXPORT int pa_fold_partials(const float* ws, void* out, int64_t cols, int64_t nparts, int dtype_acc,
                                hipStream_t st);
 
+// moe_decode.hip
+PA_EXPORT int pa_moe_decode_plan(const void* logits, int dtype, int T, int E, int topk, int norm, float* val, int* idx,
+                                 int* offs, int* perm, int* pos, int* active, int* n_active, hipStream_t st);
+PA_EXPORT int pa_moe_decode_splits(int n, int E, int d, int f);
+PA_EXPORT int pa_moe_decode_ffn(const void* x, const void* w1, const void* w2, const void* b1, const void* b2,
+                                const float* val, const int* idx, const int* offs, const int* perm, const int* pos,
+                                const int* active, const int* n_active, void* h, float* ws, void* out, int T, int E,
+                                int topk, int d, int f, int splits, hipStream_t st);
+
 // mx.hip
 PA_EXPORT int pa_mx_quant(const void* x, void* q, void* scales, int64_t R, int64_t K, int in_dtype, int fmt,
                           hipStream_t st);

@@ -159,6 +159,10 @@ SIGS = {
     "pa_grouped_gemm": [_i32, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i64, _i32, _i32, _i32, _i64, _i64, _i64, _i32,
                         _vp],
     "pa_moe_route": [_vp, _i32, _i32, _vp, _vp, _vp, _vp],
+    # MoE decode: gate + routing plan and the grouped small-M expert FFN (csrc/kernels/moe_decode.hip)
+    "pa_moe_decode_plan": [_vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "pa_moe_decode_splits": [_i32, _i32, _i32, _i32],
+    "pa_moe_decode_ffn": [_vp] * 15 + [_i32] * 6 + [_vp],
     "pa_version": [],
 }
 

@@ -119,3 +119,78 @@ def grouped_linear(x, w, offs, bias=None):
         return _fallback(x, w, offs, bias)
     y = _GroupedLinear.apply(x, w, offs.to(torch.int32).contiguous(), bias)
     return y
+
+
+# ------------------------------------------------------------------------------------- decode (T <= 64)
+# csrc/kernels/moe_decode.hip: gate + routing in one workgroup (pa_moe_decode_plan), then up projection with
+# SwiGLU, K-split down projection and combine behind pa_moe_decode_ffn. Inference only.
+DECODE_MAX_TOKENS, DECODE_MAX_EXPERTS, DECODE_MAX_TOPK = 64, 256, 8
+# fused_moe takes the decode kernels up to this many tokens: measured ahead of the grouped path on every shape at
+# 1 / 4 / 16 tokens; at 64 within +-6 % of it and behind on one shape (profiles/moe_decode.md)
+DECODE_DISPATCH_TOKENS = 16
+USE_DECODE = True  # False: fused_moe keeps the grouped path at every size (tools/bench_moe_decode.py's yardstick)
+
+
+def _decode_plan_ok(logits, topk):
+    return (logits.dim() == 2 and 1 <= logits.shape[0] <= DECODE_MAX_TOKENS
+            and 1 <= logits.shape[1] <= DECODE_MAX_EXPERTS and 1 <= topk <= min(DECODE_MAX_TOPK, logits.shape[1])
+            and L.hip_enabled_for(logits) and L.has("pa_moe_decode_plan"))
+
+
+def decode_plan(logits, topk, norm=True):
+    """Gate and routing of a decode step in one launch. logits [T, E] (T <= 64, E <= 256, topk <= min(8, E)) ->
+    (val [T, topk] fp32, idx [T, topk] int32, offs [E + 1] int32, perm [n] int32 (sorted row -> entry, the stable
+    order ``route`` gives), pos [n] int32 (entry -> sorted row), active [min(E, n)] int32 (the non-empty experts,
+    ascending, -1 behind them), n_active [1] int32), n = T * topk: softmax in fp32, the topk largest (the lower
+    expert index wins a tie), renormalised to sum 1 when ``norm``."""
+    if not _decode_plan_ok(logits, topk):
+        raise ValueError("decode_plan: needs a device tensor [T <= 64, E <= 256] and topk <= min(8, E)")
+    if logits.dtype not in (torch.float32, torch.bfloat16):
+        logits = logits.float()
+    logits = logits.detach().contiguous()
+    T, E = logits.shape
+    n, slots = T * topk, min(E, T * topk)
+    val = torch.empty(T, topk, dtype=torch.float32, device=logits.device)
+    meta = torch.empty(3 * n + E + 1 + slots + 1, dtype=torch.int32, device=logits.device)
+    idx, offs, perm, pos, active, n_active = meta.split([n, E + 1, n, n, slots, 1])
+    L.call("pa_moe_decode_plan", L.ptr(logits), L.dcode(logits), T, E, topk, int(bool(norm)), L.ptr(val), L.ptr(idx),
+           L.ptr(offs), L.ptr(perm), L.ptr(pos), L.ptr(active), L.ptr(n_active), L.stream_ptr())
+    return val, idx.view(T, topk), offs, perm, pos, active, n_active
+
+
+def decode_splits(n, E, d, f):
+    """K splits the down projection of the decode FFN runs with by default (pa_moe_decode_splits)."""
+    return int(L.lib().pa_moe_decode_splits(n, E, d, f))
+
+
+def moe_decode_ffn(x, logits, w1, w2, b1=None, b2=None, topk=2, norm_topk_prob=True, splits=None):
+    """SwiGLU expert FFN of a decode step: x [T, d], gate logits [T, E], w1 [E, d, 2f], w2 [E, f, d], b1 [E, 2f],
+    b2 [E, d] -> [T, d] bf16, out[t] = sum_j val[t, j] (swiglu(x[t] w1[e] + b1[e]) w2[e] + b2[e]), e = idx[t, j].
+    ``splits`` K splits of the down projection (None: decode_splits; must divide f / 64). Returns None when the
+    shapes, dtypes or device are not the kernels' (T <= 64, E <= 256, topk <= min(8, E), d % 64 == f % 64 == 0,
+    contiguous bf16 operands on the device): the caller keeps its own path."""
+    bf = torch.bfloat16
+    if x.dim() != 2 or logits.dim() != 2 or w1.dim() != 3 or w2.dim() != 3 or logits.shape[0] != x.shape[0]:
+        return None
+    (T, d), E, f = x.shape, w1.shape[0], w2.shape[1]
+    ok = (_decode_plan_ok(logits, topk) and L.has("pa_moe_decode_ffn") and logits.shape[1] == E
+          and tuple(w1.shape) == (E, d, 2 * f) and tuple(w2.shape) == (E, f, d) and d % 64 == 0 and f % 64 == 0
+          and d > 0 and f > 0 and (b1 is None or tuple(b1.shape) == (E, 2 * f))
+          and (b2 is None or tuple(b2.shape) == (E, d))
+          and all(t is None or (t.dtype == bf and t.is_contiguous() and t.device == x.device)
+                  for t in (x, w1, w2, b1, b2)))
+    if not ok:
+        return None
+    n = T * topk
+    if splits is None:
+        splits = decode_splits(n, E, d, f)
+    elif splits < 1 or (f // 64) % splits:
+        raise ValueError(f"moe_decode_ffn: splits ({splits}) must divide f / 64 ({f // 64})")
+    val, idx, offs, perm, pos, active, n_active = decode_plan(logits, topk, norm_topk_prob)
+    h = torch.empty(n, f, dtype=bf, device=x.device)
+    ws = torch.empty(splits, n, d, dtype=torch.float32, device=x.device)
+    out = torch.empty(T, d, dtype=bf, device=x.device)
+    L.call("pa_moe_decode_ffn", *(L.ptr(t.detach() if t is not None else None) for t in (x, w1, w2, b1, b2)),
+           L.ptr(val), L.ptr(idx), L.ptr(offs), L.ptr(perm), L.ptr(pos), L.ptr(active), L.ptr(n_active), L.ptr(h),
+           L.ptr(ws), L.ptr(out), T, E, topk, d, f, int(splits), L.stream_ptr())
+    return out

@@ -336,24 +336,33 @@ def fused_moe(x, gate_weight, ffn1_weight, ffn2_weight, ffn1_bias=None, ffn1_sca
               ffn2_scale=None, quant_method="None", moe_topk=2, norm_topk_prob=True):
     """All experts local: route with the gate *logits* ``gate_weight`` [.., E], SwiGLU FFN per expert
     (ffn1 [E, d, 2f] -> swiglu -> ffn2 [E, f, d]); routing and both projections run on the device as grouped
-    GEMMs over the expert-sorted tokens (no host sync)."""
+    GEMMs over the expert-sorted tokens (no host sync). At most ops.moe.DECODE_DISPATCH_TOKENS tokens with
+    nothing to differentiate (decode) run the gate and the FFN in ops.moe.moe_decode_ffn's kernels instead, where
+    their shapes fit."""
     from .. import ops as _ops
+    from ..ops import moe as M
     xt = x._t
     d = xt.shape[-1]
     xf = xt.reshape(-1, d)
-    g = gate_weight._t.reshape(xf.shape[0], -1).float()
+    E = ffn1_weight.shape[0]
+    b1 = ffn1_bias._t.reshape(E, -1) if ffn1_bias is not None else None
+    b2 = ffn2_bias._t.reshape(E, -1) if ffn2_bias is not None else None
+    gl = gate_weight._t.reshape(xf.shape[0], -1)
+    if (M.USE_DECODE and 0 < xf.shape[0] <= M.DECODE_DISPATCH_TOKENS and quant_method == "None" and xf.is_cuda
+            and not (torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (
+                xt, gl, ffn1_weight._t, ffn2_weight._t, b1, b2)))):
+        out = M.moe_decode_ffn(xf.contiguous(), gl, ffn1_weight._t, ffn2_weight._t, b1, b2, moe_topk, norm_topk_prob)
+        if out is not None:
+            return _wrap(out.reshape(xt.shape))
+    g = gl.float()
     probs = torch.softmax(g, -1)
     val, idx = probs.topk(moe_topk, -1)
     if norm_topk_prob:
         val = val / val.sum(-1, keepdim=True)
-    from ..ops import moe as M
     N, K = idx.shape
-    E = ffn1_weight.shape[0]
     offs, perm = M.route(idx.reshape(-1), E)
     tok = perm // K
     wts = val.reshape(-1)[perm]
-    b1 = ffn1_bias._t.reshape(E, -1) if ffn1_bias is not None else None
-    b2 = ffn2_bias._t.reshape(E, -1) if ffn2_bias is not None else None
     h = M.grouped_linear(xf[tok], ffn1_weight._t, offs, b1)
     h = _ops.swiglu(h)
     y = M.grouped_linear(h, ffn2_weight._t, offs, b2)

@@ -1,0 +1,124 @@
+"""MoE decode microbenchmark: incubate.nn.functional.fused_moe at T = 1 / 4 / 16 / 64 tokens on the decode kernels
+(csrc/kernels/moe_decode.hip) against the same call on the grouped path (ops.moe.USE_DECODE = False: torch gate math,
+pa_moe_route, gathers, pa_grouped_gemm + swiglu + pa_grouped_gemm, index_add), eager and replayed from a hipGraph.
+
+Method (tools/bench_fp8_linear.py's): one process, device events around each call, a 512 MiB buffer rewritten before
+every timed call (cold L2 / Infinity Cache: in a real step the weights stream from HBM), the contenders interleaved
+call by call, median and min-max of the repeats. The stream rate is the bf16 bytes of w1[e] and w2[e] of the experts
+the gate picked, over the median time. Launches are the device kernels a profiler sees in one eager call.
+
+    python tools/bench_moe_decode.py --out profiles/moe_decode_tables.md [--reps 9]
+"""
+import argparse
+import statistics
+import sys
+import time
+
+import torch
+
+sys.path.insert(0, ".")
+from bench_fp8_linear import Flusher, fmt_ms, interleaved  # noqa: E402  (tools/ is the script's directory)
+import paddlepaddle_amd as paddle  # noqa: E402
+from paddlepaddle_amd.ops import _loader as L  # noqa: E402
+from paddlepaddle_amd.ops import moe as M  # noqa: E402
+
+# (d, f, E, topk)
+SHAPES = [(4096, 14336, 8, 2), (2048, 1408, 64, 6), (7168, 2048, 256, 8)]
+TOKENS = [1, 4, 16, 64]
+NAMES = ["grouped", "decode", "grouped graph", "decode graph"]
+fused_moe = paddle.incubate.nn.functional.fused_moe
+
+
+def call(args, k, decode):
+    """fused_moe on the grouped path, or on the decode kernels at every token count they take (fused_moe's own
+    threshold, ops.moe.DECODE_DISPATCH_TOKENS, comes from this table)."""
+    keep = M.DECODE_DISPATCH_TOKENS
+    M.USE_DECODE, M.DECODE_DISPATCH_TOKENS = decode, M.DECODE_MAX_TOKENS
+    try:
+        return fused_moe(*args, moe_topk=k)
+    finally:
+        M.USE_DECODE, M.DECODE_DISPATCH_TOKENS = True, keep
+
+
+def graphed(args, k, decode):
+    s = torch.cuda.Stream()
+    s.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(s):
+        call(args, k, decode)
+    torch.cuda.current_stream().wait_stream(s)
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g):
+        out = call(args, k, decode)
+    return g, out
+
+
+def launches(fn):
+    """Device kernels of one call, or None where the profiler gives no device events."""
+    try:
+        from torch.profiler import ProfilerActivity, profile
+        with profile(activities=[ProfilerActivity.CPU, ProfilerActivity.CUDA]) as prof:
+            fn()
+            torch.cuda.synchronize()
+        n = sum(1 for e in prof.events() if e.device_type == torch.autograd.DeviceType.CUDA
+                and not e.name.lower().startswith(("memcpy", "memset")))
+        return n or None
+    except Exception as e:  # noqa: BLE001  (reported in the table, the timings stand without it)
+        print(f"profiler: {e}", flush=True)
+        return None
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", default="profiles/moe_decode_tables.md")
+    ap.add_argument("--reps", type=int, default=9)
+    ap.add_argument("--no-launch-count", action="store_true")
+    a = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("bench_moe_decode needs a HIP device")
+    flush = Flusher()
+    p = torch.cuda.get_device_properties(0)
+    lines = ["# MoE decode: fused_moe on the decode kernels against the grouped path", "",
+             f"Box: {torch.cuda.get_device_name(0)} ({p.gcnArchName}, {p.multi_processor_count} CUs), torch "
+             f"{torch.__version__}. Date: {time.strftime('%Y-%m-%d')}. Written by `tools/bench_moe_decode.py --reps "
+             f"{a.reps}`: cold caches, device events, contenders interleaved; each time is the median of {a.reps} calls "
+             "in ms with (min-max) behind it. `grouped`: the path fused_moe took before the decode kernels. `graph`: "
+             "the same call replayed from a hipGraph. `TB/s`: weight bytes of the active experts over the median "
+             "time of `decode graph` / `grouped graph`. `max diff`: largest difference of the two outputs over the "
+             "largest output magnitude.", "",
+             "| d / f / E / top-k | T | active | splits | " + " | ".join(NAMES) +
+             " | launches grouped / decode | TB/s decode / grouped | max diff |", "|" + "---|" * 11]
+    for d, f, E, k in SHAPES:
+        w1 = paddle.Tensor(torch.empty(E, d, 2 * f, dtype=torch.bfloat16, device="cuda").normal_(0, d ** -0.5))
+        w2 = paddle.Tensor(torch.empty(E, f, d, dtype=torch.bfloat16, device="cuda").normal_(0, f ** -0.5))
+        for T in TOKENS:
+            torch.manual_seed(T)
+            args = (paddle.Tensor(torch.randn(T, d, device="cuda").bfloat16()),
+                    paddle.Tensor(torch.randn(T, E, device="cuda")), w1, w2)
+            n_act = int(M.decode_plan(args[1]._t, k)[6])
+            n0 = L.calls("pa_moe_decode_ffn"), L.calls("pa_grouped_gemm")
+            o_old, o_new = call(args, k, False)._t.float(), call(args, k, True)._t.float()
+            assert L.calls("pa_moe_decode_ffn") == n0[0] + 1 and L.calls("pa_grouped_gemm") == n0[1] + 2
+            diff = float((o_old - o_new).abs().max() / o_old.abs().max())
+            g_old, g_new = graphed(args, k, False), graphed(args, k, True)
+            variants = {"grouped": (lambda: call(args, k, False), None), "decode": (lambda: call(args, k, True), None),
+                        "grouped graph": (g_old[0].replay, None), "decode graph": (g_new[0].replay, None)}
+            res = interleaved(variants, a.reps, flush, warmup=2)
+            nl = (None, None) if a.no_launch_count else (launches(lambda: call(args, k, False)),
+                                                         launches(lambda: call(args, k, True)))
+            wbytes = n_act * 3 * d * f * 2
+            tb = [wbytes / (statistics.median(res[n]) * 1e-3) / 1e12 for n in ("decode graph", "grouped graph")]
+            lines.append(f"| {d} / {f} / {E} / {k} | {T} | {n_act} | {M.decode_splits(T * k, E, d, f)} | "
+                         + " | ".join(fmt_ms(res[n]) for n in NAMES)
+                         + f" | {nl[0] or 'not measured'} / {nl[1] or 'not measured'} | {tb[0]:.2f} / {tb[1]:.2f} | "
+                         f"{diff:.4f} |")
+            print(lines[-1], flush=True)
+            with open(a.out, "w") as fh:
+                fh.write("\n".join(lines) + "\n")
+            del g_old, g_new
+        del w1, w2
+        torch.cuda.empty_cache()
+    print(f"wrote {a.out}")
+
+
+if __name__ == "__main__":
+    main()
