@@ -19,8 +19,26 @@
 //     written (each sorted row belongs to exactly one expert), so there is no memset and no atomic.
 //   * moe_decode_combine_k sums slabs, bias and the token's experts in a fixed ascending order: bit-identical
 //     from run to run.
+//
+// MXFP4 expert weights (pa_moe_decode_up_mx / pa_moe_decode_down_mx; formats in mx.hip): the same plan and the same
+// combine around two projections built like mx.hip's gemm_mx_small_m_k instead of the LDS ring, since 4.25-bit weights
+// leave nothing to stage: w1_q [E, 2f, d / 2] and w2_q [E, d, f / 2] are K-major per expert, a lane's 16-byte weight
+// fragment and its E8M0 byte go from global memory into v_mfma_scale_f32_16x16x128_f8f6f4 two of its wave's steps
+// ahead, the four waves interleave the 128-k steps and their sums meet in LDS in wave order. Activations are mxfp8 at
+// both projections: x is quantised once by pa_mx_quant ([T, d] codes + [T, d / 32] scales) and gathered through
+// perm[row] / topk in the lane's pointers; the up kernel owns 32 value channels and the 32 gate channels f + n, one
+// 32-block of h, so bias + silu(value) * gate, the block's amax, its E8M0 byte and the e4m3 codes (mx_block.h, the
+// quantiser's own rule) all happen in its epilogue and h exists only as h_q [n, f] + h_s [n, f / 32]. The loop over
+// 16-row fragments runs to ceil(cnt / 16) of the expert's own count (uniform in the workgroup), not to a template
+// parameter from T: at 64 tokens over many experts most experts hold one or two rows. The accumulators stay
+// statically indexed (unrolled over 4, skipped on the uniform predicate). The down projection splits K = f over
+// gridDim.z in whole 128-k steps into the same fp32 slabs, which moe_decode_combine_k sums.
+//   Deviations from the plain sketch: the cross-wave reduction runs one row fragment at a time through a 16-KiB (up)
+// / 8-KiB (down) buffer instead of holding all four fragments (64 KiB) at once; it costs two barriers per live
+// fragment and keeps LDS out of what limits occupancy (registers do: 2 waves a SIMD up, 3 down).
 #include "launch.h"
 #include "mfma_tile.h"
+#include "mx_block.h"
 
 namespace pa {
 namespace {
@@ -301,6 +319,214 @@ bool moe_decode_shape_ok(int T, int E, int topk, int d, int f) {
          d >= kMdBK && f >= kMdBK && d % 64 == 0 && f % 64 == 0;
 }
 
+// ------------------------------------------------------------------------------------------------ MXFP4 experts
+struct MoeDecMxArgs {
+  const uint8_t *xq, *xs;    // [T, d] e4m3fn, [T, d / 32]
+  const uint8_t *w1q, *w1s;  // [E, 2f, d / 2] e2m1 pairs, [E, 2f, d / 32]
+  const uint8_t *w2q, *w2s;  // [E, d, f / 2], [E, d, f / 32]
+  const uint16_t* b1;        // [E, 2f] bf16 or null
+  const int *offs, *perm, *active, *n_active;
+  uint8_t *hq, *hs;          // [n, f] e4m3fn, [n, f / 32], sorted row order
+  float* ws;                 // [splits, n, d] fp32
+  int T, E, topk, d, f, n, steps_per;
+};
+
+constexpr int kMxBand = 32;  // channels of a workgroup's band: one 32-block of h in the up projection
+
+// the expert of this slot and its sorted rows [r0, r0 + cnt); false for a slot with nothing to do or a plan that
+// does not fit the buffers
+__device__ __forceinline__ bool moe_mx_slot(const MoeDecMxArgs& p, int slot, int& e, int& r0, int& cnt) {
+  if (slot >= *p.n_active) return false;
+  e = p.active[slot];
+  if ((unsigned)e >= (unsigned)p.E) return false;
+  r0 = p.offs[e];
+  if (r0 < 0 || r0 >= p.n) return false;
+  cnt = min(min(p.offs[e + 1] - r0, kMdMaxT), p.n - r0);
+  return cnt > 0;
+}
+
+// The K loop of both projections: this wave's 128-k steps wave, wave + 4, ... of nst. wrow / wsc: the lane's weight
+// row (channel lane & 15 of each 16-channel tile) and its scale bytes at k-group lane >> 4 of step 0; arow / asc: the
+// same for the lane's mxfp8 activation row of each 16-row fragment. The weight stream, the only operand that comes
+// from HBM, runs two of the wave's steps ahead of the MFMAs; the activations are L2 hits. Fragments past nfrag
+// (wave-uniform) are skipped, the accumulators stay statically indexed.
+template <int NT>
+__device__ __forceinline__ void moe_mx_stream(const uint8_t* const (&wrow)[NT], const uint8_t* const (&wsc)[NT],
+                                              const uint8_t* const (&arow)[4], const uint8_t* const (&asc)[4],
+                                              int nfrag, int nst, int wave, f32x4 (&acc)[4][NT]) {
+#pragma unroll
+  for (int t = 0; t < 4; ++t)
+#pragma unroll
+    for (int j = 0; j < NT; ++j) acc[t][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+  uint4 raw0[NT], raw1[NT];
+  int s0[NT], s1[NT];
+#pragma unroll
+  for (int j = 0; j < NT; ++j) {
+    const bool h0 = wave < nst, h1 = wave + 4 < nst;
+    raw0[j] = h0 ? *reinterpret_cast<const uint4*>(wrow[j] + wave * 64) : make_uint4(0, 0, 0, 0);
+    s0[j] = h0 ? (int)wsc[j][wave * 4] : 127;
+    raw1[j] = h1 ? *reinterpret_cast<const uint4*>(wrow[j] + (wave + 4) * 64) : make_uint4(0, 0, 0, 0);
+    s1[j] = h1 ? (int)wsc[j][(wave + 4) * 4] : 127;
+  }
+  for (int c = wave; c < nst; c += 4) {
+    i32x8 bf[NT];
+    int bs[NT];
+#pragma unroll
+    for (int j = 0; j < NT; ++j) {
+      bf[j] = widen(raw0[j]);
+      bs[j] = s0[j];
+      raw0[j] = raw1[j];
+      s0[j] = s1[j];
+      const bool h = c + 8 < nst;
+      raw1[j] = h ? *reinterpret_cast<const uint4*>(wrow[j] + (int64_t)(c + 8) * 64) : make_uint4(0, 0, 0, 0);
+      s1[j] = h ? (int)wsc[j][(c + 8) * 4] : 127;
+    }
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+      if (t >= nfrag) continue;
+      const uint8_t* ap = arow[t] + (int64_t)c * 128;
+      const i32x8 af = join(*reinterpret_cast<const uint4*>(ap), *reinterpret_cast<const uint4*>(ap + 64));
+      const int as = (int)asc[t][c * 4];
+#pragma unroll
+      for (int j = 0; j < NT; ++j)
+        acc[t][j] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(af, bf[j], acc[t][j], kFmtFp8, kFmtFp4, 0, as, 0,
+                                                                     bs[j]);
+    }
+  }
+}
+
+// one fragment's partial sums of this wave into red[wave]: tile j at j * 256, [16 rows][16 channels]. The MFMA leaves
+// channel lane & 15 and rows 4 (lane >> 4) + r in the lane.
+template <int NT>
+__device__ __forceinline__ void moe_mx_put(float (&red)[4][NT * 256], const f32x4 (&a)[NT], int wave, int lane) {
+#pragma unroll
+  for (int j = 0; j < NT; ++j)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) red[wave][j * 256 + ((lane >> 4) * 4 + r) * 16 + (lane & 15)] = a[j][r];
+}
+template <int NT>
+__device__ __forceinline__ float moe_mx_sum(const float (&red)[4][NT * 256], int i) {
+  return ((red[0][i] + red[1][i]) + red[2][i]) + red[3][i];
+}
+
+// Up projection + SwiGLU + mxfp8 quantisation of h. grid (f / 32, slots). Tiles 0, 1: value channels [n0, n0 + 32);
+// tiles 2, 3: gate channels [f + n0, f + n0 + 32).
+__global__ __launch_bounds__(256) void moe_decode_up_mx_k(MoeDecMxArgs p) {
+  constexpr int NT = 4;
+  __shared__ float red[4][NT * 256];
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const int col = lane & 15, g = lane >> 4;
+  int e, r0, cnt;
+  if (!moe_mx_slot(p, blockIdx.y, e, r0, cnt)) return;
+  const int n0 = blockIdx.x * kMxBand, nfrag = (cnt + 15) >> 4;
+  const int ldq = p.d / 2, lds = p.d / 32;
+  const uint8_t* wrow[NT];
+  const uint8_t* wsc[NT];
+#pragma unroll
+  for (int j = 0; j < NT; ++j) {
+    const int64_t ch = (int64_t)e * 2 * p.f + (j < 2 ? n0 + j * 16 : p.f + n0 + (j - 2) * 16) + col;
+    wrow[j] = p.w1q + ch * ldq + g * 16;
+    wsc[j] = p.w1s + ch * lds + g;
+  }
+  // row gather: the token of the lane's row of each fragment; rows past the count are clamped reads, never stored
+  const uint8_t* arow[4];
+  const uint8_t* asc[4];
+#pragma unroll
+  for (int t = 0; t < 4; ++t) {
+    const int m = min(t * 16 + col, cnt - 1);
+    const int tok = min(max(p.perm[r0 + m] / p.topk, 0), p.T - 1);
+    arow[t] = p.xq + (int64_t)tok * p.d + g * 16;
+    asc[t] = p.xs + (int64_t)tok * lds + g;
+  }
+  f32x4 acc[4][NT];
+  moe_mx_stream<NT>(wrow, wsc, arow, asc, nfrag, p.d / 128, wave, acc);
+
+  // epilogue, a fragment at a time: thread -> row tid >> 4 of the fragment, channels 2 (tid & 15) + {0, 1} of the
+  // band; the row's 32-block is the 16 lanes of one DPP row
+  const int ml = tid >> 4, c2 = (tid & 15) * 2;
+  float ba[2] = {0.f, 0.f}, bg[2] = {0.f, 0.f};
+  if (p.b1) {
+    const uint16_t* b = p.b1 + (int64_t)e * 2 * p.f + n0 + c2;
+    const uint32_t va = *reinterpret_cast<const uint32_t*>(b), vg = *reinterpret_cast<const uint32_t*>(b + p.f);
+    ba[0] = lo_bf16(va); ba[1] = hi_bf16(va); bg[0] = lo_bf16(vg); bg[1] = hi_bf16(vg);
+  }
+#pragma unroll
+  for (int t = 0; t < 4; ++t) {
+    if (t >= nfrag) continue;
+    moe_mx_put<NT>(red, acc[t], wave, lane);
+    __syncthreads();
+    float h[2];
+#pragma unroll
+    for (int q = 0; q < 2; ++q) {
+      const int i = ((c2 + q) >> 4) * 256 + ml * 16 + ((c2 + q) & 15);
+      const float a = moe_mx_sum<NT>(red, i) + ba[q], gt = moe_mx_sum<NT>(red, i + 512) + bg[q];
+      h[q] = silu(a) * gt;
+    }
+    float amax = fmaxf(fabsf(h[0]), fabsf(h[1]));
+#pragma unroll
+    for (int o = 1; o < 16; o <<= 1) amax = fmaxf(amax, __shfl_xor(amax, o, 64));
+    const int eb = mx_block_exp<8>(amax);
+    const uint32_t code = mx_e4m3x2<false>(h[0], h[1], mx_block_mult(eb), 0);
+    const int m = t * 16 + ml;
+    if (m < cnt) {
+      *reinterpret_cast<uint16_t*>(p.hq + (int64_t)(r0 + m) * p.f + n0 + c2) = (uint16_t)(code & 0xffffu);
+      if ((tid & 15) == 0) p.hs[(int64_t)(r0 + m) * (p.f / 32) + blockIdx.x] = (uint8_t)eb;
+    }
+    __syncthreads();
+  }
+}
+
+// Down projection: rows of h_q x one 32-channel band of w2_q[e] over the 128-k steps of split blockIdx.z -> fp32
+// slab. grid (d / 32, slots, splits).
+__global__ __launch_bounds__(256) void moe_decode_down_mx_k(MoeDecMxArgs p) {
+  constexpr int NT = 2;
+  __shared__ float red[4][NT * 256];
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const int col = lane & 15, g = lane >> 4;
+  int e, r0, cnt;
+  if (!moe_mx_slot(p, blockIdx.y, e, r0, cnt)) return;
+  const int n0 = blockIdx.x * kMxBand, nfrag = (cnt + 15) >> 4;
+  const int step0 = blockIdx.z * p.steps_per, nst = min(p.steps_per, p.f / 128 - step0);
+  const int ldq = p.f / 2, lds = p.f / 32;
+  const uint8_t* wrow[NT];
+  const uint8_t* wsc[NT];
+#pragma unroll
+  for (int j = 0; j < NT; ++j) {
+    const int64_t ch = (int64_t)e * p.d + n0 + j * 16 + col;
+    wrow[j] = p.w2q + ch * ldq + (int64_t)step0 * 64 + g * 16;
+    wsc[j] = p.w2s + ch * lds + step0 * 4 + g;
+  }
+  const uint8_t* arow[4];
+  const uint8_t* asc[4];
+#pragma unroll
+  for (int t = 0; t < 4; ++t) {
+    const int64_t row = r0 + min(t * 16 + col, cnt - 1);
+    arow[t] = p.hq + row * p.f + (int64_t)step0 * 128 + g * 16;
+    asc[t] = p.hs + row * lds + step0 * 4 + g;
+  }
+  f32x4 acc[4][NT];
+  moe_mx_stream<NT>(wrow, wsc, arow, asc, nfrag, nst, wave, acc);
+
+  float* slab = p.ws + ((int64_t)blockIdx.z * p.n + r0) * p.d + n0;
+#pragma unroll
+  for (int t = 0; t < 4; ++t) {
+    if (t >= nfrag) continue;
+    moe_mx_put<NT>(red, acc[t], wave, lane);
+    __syncthreads();
+#pragma unroll
+    for (int q = 0; q < 2; ++q) {  // thread -> rows (tid >> 5) + 8 q, channel tid & 31: a row's band is 128 bytes
+      const int ml = (tid >> 5) + 8 * q, c = tid & 31, m = t * 16 + ml;
+      const float v = moe_mx_sum<NT>(red, (c >> 4) * 256 + ml * 16 + (c & 15));
+      if (m < cnt) slab[(int64_t)m * p.d + c] = v;
+    }
+    __syncthreads();
+  }
+}
+
+bool moe_decode_mx_shape_ok(int T, int E, int topk, int d, int f) {
+  return moe_decode_shape_ok(T, E, topk, d, f) && d % 128 == 0 && f % 128 == 0;
+}
+
 }  // namespace
 }  // namespace pa
 
@@ -359,5 +585,60 @@ PA_EXPORT int pa_moe_decode_ffn(const void* x, const void* w1, const void* w2, c
   const int rc = mt == 1 ? run(IntC<1>{}) : mt == 2 ? run(IntC<2>{}) : mt == 3 ? run(IntC<3>{}) : run(IntC<4>{});
   if (rc) return rc;
   hipLaunchKernelGGL(moe_decode_combine_k, dim3((d / 4 + 255) / 256, T), dim3(256), 0, st, p);
+  return (int)hipGetLastError();
+}
+
+// K splits of the MXFP4 down projection by default: the fewest (at most 8, at least two 128-k steps each) that give
+// every compute unit two workgroups if all min(E, n) slots are active, evened out so that no split is empty.
+PA_EXPORT int pa_moe_decode_mx_splits(int n, int E, int d, int f) {
+  if (n < 1 || E < 1 || d < 128 || f < 128) return 1;
+  const int64_t wgs = (int64_t)(d / kMxBand) * (E < n ? E : n), target = 2 * device_cus();
+  const int steps = f / 128, most = steps / 2 < 8 ? (steps / 2 < 1 ? 1 : steps / 2) : 8;
+  int s = (int)((target + wgs - 1) / wgs);
+  s = s < most ? s : most;
+  const int per = (steps + s - 1) / s;
+  return (steps + per - 1) / per;
+}
+
+// Up projection of the MXFP4 expert FFN on a plan of pa_moe_decode_plan: xq [T, d] e4m3fn + xs [T, d / 32] (pa_mx_quant
+// of x, mxfp8), w1q [E, 2f, d / 2] + w1s [E, 2f, d / 32] (mxfp4, K-major per expert), b1 [E, 2f] bf16 or null ->
+// hq [n, f] e4m3fn + hs [n, f / 32], the mxfp8 quantisation of silu(value) * gate in sorted row order (n = T * topk;
+// neither needs clearing). d % 128 == 0, f % 128 == 0.
+PA_EXPORT int pa_moe_decode_up_mx(const void* xq, const void* xs, const void* w1q, const void* w1s, const void* b1,
+                                  const int* offs, const int* perm, const int* active, const int* n_active, void* hq,
+                                  void* hs, int T, int E, int topk, int d, int f, hipStream_t st) {
+  if (!moe_decode_mx_shape_ok(T, E, topk, d, f)) return 1;
+  MoeDecMxArgs p{};
+  p.xq = (const uint8_t*)xq; p.xs = (const uint8_t*)xs; p.w1q = (const uint8_t*)w1q; p.w1s = (const uint8_t*)w1s;
+  p.b1 = (const uint16_t*)b1; p.offs = offs; p.perm = perm; p.active = active; p.n_active = n_active;
+  p.hq = (uint8_t*)hq; p.hs = (uint8_t*)hs;
+  p.T = T; p.E = E; p.topk = topk; p.d = d; p.f = f; p.n = T * topk;
+  hipLaunchKernelGGL(moe_decode_up_mx_k, dim3(f / kMxBand, E < p.n ? E : p.n), dim3(256), 0, st, p);
+  return (int)hipGetLastError();
+}
+
+// Down projection and combine: hq / hs as pa_moe_decode_up_mx leaves them, w2q [E, d, f / 2] + w2s [E, d, f / 32],
+// b2 [E, d] bf16 or null, ws = splits * n * d fp32 of workspace (need not be cleared) -> out [T, d] bf16. splits in
+// [1, f / 128] with no empty split (as pa_moe_decode_mx_splits returns; 1 is always valid).
+PA_EXPORT int pa_moe_decode_down_mx(const void* hq, const void* hs, const void* w2q, const void* w2s, const void* b2,
+                                    const float* val, const int* idx, const int* offs, const int* pos,
+                                    const int* active, const int* n_active, float* ws, void* out, int T, int E,
+                                    int topk, int d, int f, int splits, hipStream_t st) {
+  if (!moe_decode_mx_shape_ok(T, E, topk, d, f)) return 1;
+  const int steps = f / 128;
+  if (splits < 1 || splits > steps) return 2;
+  const int per = (steps + splits - 1) / splits;
+  if ((steps + per - 1) / per != splits) return 2;
+  MoeDecMxArgs p{};
+  p.w2q = (const uint8_t*)w2q; p.w2s = (const uint8_t*)w2s; p.offs = offs; p.active = active; p.n_active = n_active;
+  p.hq = (uint8_t*)hq; p.hs = (uint8_t*)hs; p.ws = ws;
+  p.T = T; p.E = E; p.topk = topk; p.d = d; p.f = f; p.n = T * topk; p.steps_per = per;
+  hipLaunchKernelGGL(moe_decode_down_mx_k, dim3(d / kMxBand, E < p.n ? E : p.n, splits), dim3(256), 0, st, p);
+  const hipError_t err = hipGetLastError();
+  if (err != hipSuccess) return (int)err;
+  MoeDecArgs c{};
+  c.b2 = (const uint16_t*)b2; c.val = val; c.idx = idx; c.pos = pos; c.ws = ws; c.out = (uint16_t*)out;
+  c.T = T; c.E = E; c.topk = topk; c.d = d; c.f = f; c.n = p.n; c.splits = splits;
+  hipLaunchKernelGGL(moe_decode_combine_k, dim3((d / 4 + 255) / 256, T), dim3(256), 0, st, c);
   return (int)hipGetLastError();
 }

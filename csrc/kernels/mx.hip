@@ -54,16 +54,13 @@
 #include "common.h"
 #include "launch.h"
 #include "mfma_tile.h"
+#include "mx_block.h"
 
 #include <algorithm>
 
 using namespace pa;
 
 namespace {
-
-typedef __attribute__((ext_vector_type(8))) int i32x8;
-
-constexpr int kFmtFp8 = 0, kFmtFp4 = 4;  // the MFMA's cbsz / blgp codes, used as the launchers' format codes
 
 // ------------------------------------------------------------------------------------------ quantiser
 
@@ -76,11 +73,6 @@ __device__ __forceinline__ uint32_t fp4_code(float v) {
   // r >= 1: exponent and top mantissa bit count the codes 2 (1.0) .. 7 (6.0); below: 0.5 -> 1, 0 -> 0
   const uint32_t mag = r >= 1.f ? (__float_as_uint(r) >> 22) - 252u : (r > 0.f ? 1u : 0u);
   return sign | mag;
-}
-
-__device__ __forceinline__ float sat448(float v) {
-  v = v > 448.f ? 448.f : v;
-  return v < -448.f ? -448.f : v;
 }
 
 __device__ __forceinline__ float quad_max(float m) {
@@ -106,9 +98,8 @@ __global__ __launch_bounds__(256) void mx_quant_k(const T* __restrict__ x, uint8
 #pragma unroll
   for (int i = 0; i < 8; ++i) m = fmaxf(m, fabsf(v[i]));
   m = quad_max(m);
-  int e = (int)(__float_as_uint(m) >> 23) - EMAX;  // floor(log2 amax) + 127 - emax (finite amax: at most 252)
-  e = m == 0.f ? 127 : (e < 0 ? 0 : e);
-  const float s = __uint_as_float((uint32_t)(254 - e) << 23);  // 2^(127 - e)
+  const int e = mx_block_exp<EMAX>(m);  // finite amax: at most 252
+  const float s = mx_block_mult(e);
   if (ok) {
     if constexpr (FMT == kFmtFp4) {
       uint32_t w = 0;
@@ -120,8 +111,7 @@ __global__ __launch_bounds__(256) void mx_quant_k(const T* __restrict__ x, uint8
 #pragma unroll
       for (int h = 0; h < 2; ++h) {
         const float* u = v + 4 * h;
-        const int lo = __builtin_amdgcn_cvt_pk_fp8_f32(sat448(u[0] * s), sat448(u[1] * s), 0, false);
-        w[h] = (uint32_t)__builtin_amdgcn_cvt_pk_fp8_f32(sat448(u[2] * s), sat448(u[3] * s), lo, true);
+        w[h] = mx_e4m3x2<true>(u[2], u[3], s, mx_e4m3x2<false>(u[0], u[1], s, 0));
       }
       reinterpret_cast<uint2*>(q)[tid] = make_uint2(w[0], w[1]);
     }
@@ -140,15 +130,6 @@ __global__ __launch_bounds__(256) void mx_quant_k(const T* __restrict__ x, uint8
 }
 
 // ------------------------------------------------------------------------------------------ shared by the GEMMs
-
-__device__ __forceinline__ i32x8 widen(uint4 v) {
-  i32x8 f = {(int)v.x, (int)v.y, (int)v.z, (int)v.w, 0, 0, 0, 0};
-  return f;
-}
-__device__ __forceinline__ i32x8 join(uint4 lo, uint4 hi) {
-  i32x8 f = {(int)lo.x, (int)lo.y, (int)lo.z, (int)lo.w, (int)hi.x, (int)hi.y, (int)hi.z, (int)hi.w};
-  return f;
-}
 
 // one output element in the launcher's out code (0 fp32, 1 fp16, 2 bf16)
 __device__ __forceinline__ void store_out(void* c, int64_t i, float v, int out) {

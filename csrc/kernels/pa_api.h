@@ -273,6 +273,14 @@ PA_EXPORT int pa_moe_decode_ffn(const void* x, const void* w1, const void* w2, c
                                 const float* val, const int* idx, const int* offs, const int* perm, const int* pos,
                                 const int* active, const int* n_active, void* h, float* ws, void* out, int T, int E,
                                 int topk, int d, int f, int splits, hipStream_t st);
+PA_EXPORT int pa_moe_decode_mx_splits(int n, int E, int d, int f);
+PA_EXPORT int pa_moe_decode_up_mx(const void* xq, const void* xs, const void* w1q, const void* w1s, const void* b1,
+                                  const int* offs, const int* perm, const int* active, const int* n_active, void* hq,
+                                  void* hs, int T, int E, int topk, int d, int f, hipStream_t st);
+PA_EXPORT int pa_moe_decode_down_mx(const void* hq, const void* hs, const void* w2q, const void* w2s, const void* b2,
+                                    const float* val, const int* idx, const int* offs, const int* pos,
+                                    const int* active, const int* n_active, float* ws, void* out, int T, int E,
+                                    int topk, int d, int f, int splits, hipStream_t st);
 
 // mx.hip
 PA_EXPORT int pa_mx_quant(const void* x, void* q, void* scales, int64_t R, int64_t K, int in_dtype, int fmt,

@@ -163,6 +163,10 @@ SIGS = {
     "pa_moe_decode_plan": [_vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "pa_moe_decode_splits": [_i32, _i32, _i32, _i32],
     "pa_moe_decode_ffn": [_vp] * 15 + [_i32] * 6 + [_vp],
+    # the same FFN over MXFP4 expert weights: up projection (+ SwiGLU + mxfp8 quantisation), down projection + combine
+    "pa_moe_decode_mx_splits": [_i32, _i32, _i32, _i32],
+    "pa_moe_decode_up_mx": [_vp] * 11 + [_i32] * 5 + [_vp],
+    "pa_moe_decode_down_mx": [_vp] * 13 + [_i32] * 6 + [_vp],
     "pa_version": [],
 }
 

@@ -15,6 +15,7 @@ from __future__ import annotations
 import torch
 
 from . import _loader as L
+from . import mx as MX
 
 _ZERO = {}
 
@@ -194,3 +195,106 @@ def moe_decode_ffn(x, logits, w1, w2, b1=None, b2=None, topk=2, norm_topk_prob=T
            L.ptr(val), L.ptr(idx), L.ptr(offs), L.ptr(perm), L.ptr(pos), L.ptr(active), L.ptr(n_active), L.ptr(h),
            L.ptr(ws), L.ptr(out), T, E, topk, d, f, int(splits), L.stream_ptr())
     return out
+
+
+# ------------------------------------------------------------------------------------- decode, MXFP4 experts
+# The same plan and combine around two projections on the block-scaled MFMA (csrc/kernels/moe_decode.hip
+# pa_moe_decode_up_mx / pa_moe_decode_down_mx): expert weights mxfp4, K-major per expert, activations mxfp8 at both
+# projections (formats in ops/mx.py). Five launches: plan, quantise x, up, down, combine. Inference only.
+CALLS = {"mx_fallback": 0}  # fused_moe(quant_method="mxfp4") calls that ran moe_ffn_mx_reference instead of the kernels
+
+
+def quantize_experts_mx(w1, w2):
+    """fused_moe's expert weights w1 [E, d, 2f], w2 [E, f, d] -> (w1_q [E, 2f, d / 2], w1_s [E, 2f, d / 32],
+    w2_q [E, d, f / 2], w2_s [E, d, f / 32]) uint8: ``mx.quantize_weight(w[e])`` stacked over e (an expert at a time,
+    so the transposed copy is one expert's), quantised where the weights are."""
+    q1, s1 = zip(*(MX.quantize_weight(w1[e]) for e in range(w1.shape[0])))
+    q2, s2 = zip(*(MX.quantize_weight(w2[e]) for e in range(w2.shape[0])))
+    return torch.stack(q1), torch.stack(s1), torch.stack(q2), torch.stack(s2)
+
+
+def moe_ffn_mx_reference(x, val, idx, w1_q, w1_s, w2_q, w2_s, b1=None, b2=None, dtype=torch.float32):
+    """What the MXFP4 expert FFN computes, in plain torch with the arithmetic in ``dtype``, for any T, on CPU or device:
+    x [T, d] is quantised to mxfp8 per row; entry (t, j) with e = idx[t, j] takes u = dq(xq[t]) . dq(w1_q[e])^T + b1[e],
+    h = silu(value half) * gate half, h quantised to mxfp8 along f by the same rule, y = dq(hq) . dq(w2_q[e])^T + b2[e];
+    out[t] = sum_j val[t, j] y. ``val`` / ``idx`` [T, topk] are the routing weights and experts. Returns [T, d] in
+    ``dtype``. The CPU path and the fallback of fused_moe(quant_method="mxfp4")."""
+    T, d = x.shape
+    dq = lambda q, s, fmt: MX.dequantize_mx(q, s, fmt, dtype)
+    xd = dq(*MX.quantize_mx(x, "mxfp8"), "mxfp8")
+    out = torch.zeros(T, d, dtype=dtype, device=x.device)
+    for e in torch.unique(idx).tolist():
+        t, j = torch.nonzero(idx == e, as_tuple=True)
+        u = xd[t] @ dq(w1_q[e], w1_s[e], "mxfp4").t()
+        if b1 is not None:
+            u = u + b1[e].to(dtype)
+        a, g = u.chunk(2, -1)
+        y = dq(*MX.quantize_mx(torch.nn.functional.silu(a) * g, "mxfp8"), "mxfp8") @ dq(w2_q[e], w2_s[e], "mxfp4").t()
+        if b2 is not None:
+            y = y + b2[e].to(dtype)
+        out.index_add_(0, t, val[t, j].to(dtype).unsqueeze(1) * y)
+    return out
+
+
+def decode_splits_mx(n, E, d, f):
+    """K splits the MXFP4 down projection runs with by default (pa_moe_decode_mx_splits; it counts 128-k steps)."""
+    return int(L.lib().pa_moe_decode_mx_splits(n, E, d, f))
+
+
+def _decode_up_mx(x_q, x_s, w1_q, w1_s, b1, plan, topk):
+    """Up projection + SwiGLU + quantisation on a ``decode_plan``: x_q [T, d] e4m3fn / x_s [T, d / 32] -> (h_q [n, f]
+    uint8 e4m3fn codes, h_s [n, f / 32]) in the plan's sorted row order."""
+    _, _, offs, perm, _, active, n_active = plan
+    (T, d), (E, f2) = x_q.shape, w1_q.shape[:2]
+    n, f = T * topk, f2 // 2
+    h_q = torch.empty(n, f, dtype=torch.uint8, device=x_q.device)
+    h_s = torch.empty(n, f // 32, dtype=torch.uint8, device=x_q.device)
+    L.call("pa_moe_decode_up_mx", L.ptr(MX._u8(x_q)), L.ptr(x_s), L.ptr(w1_q), L.ptr(w1_s), L.ptr(b1), L.ptr(offs),
+           L.ptr(perm), L.ptr(active), L.ptr(n_active), L.ptr(h_q), L.ptr(h_s), T, E, topk, d, f, L.stream_ptr())
+    return h_q, h_s
+
+
+def _decode_down_mx(h_q, h_s, w2_q, w2_s, b2, plan, topk, splits=None):
+    """Down projection (K = f split ``splits`` ways, None: decode_splits_mx) and combine on a ``decode_plan``:
+    h_q [n, f] / h_s [n, f / 32] in sorted row order -> out [T, d] bf16."""
+    val, idx, offs, _, pos, active, n_active = plan
+    (n, f), (E, d) = h_q.shape, w2_q.shape[:2]
+    T, steps = n // topk, f // 128
+    if splits is None:
+        splits = decode_splits_mx(n, E, d, f)
+    elif not 1 <= splits <= steps or -(-steps // (-(-steps // splits))) != splits:  # ceil(steps / per) == splits
+        raise ValueError(f"_decode_down_mx: splits ({splits}) must split {steps} k-steps with no empty split")
+    ws = torch.empty(splits, n, d, dtype=torch.float32, device=h_q.device)
+    out = torch.empty(T, d, dtype=torch.bfloat16, device=h_q.device)
+    L.call("pa_moe_decode_down_mx", L.ptr(MX._u8(h_q)), L.ptr(h_s), L.ptr(w2_q), L.ptr(w2_s), L.ptr(b2), L.ptr(val),
+           L.ptr(idx), L.ptr(offs), L.ptr(pos), L.ptr(active), L.ptr(n_active), L.ptr(ws), L.ptr(out), T, E, topk, d,
+           f, int(splits), L.stream_ptr())
+    return out
+
+
+def moe_decode_ffn_mx(x, logits, w1_q, w1_s, w2_q, w2_s, b1=None, b2=None, topk=2, norm_topk_prob=True, splits=None):
+    """SwiGLU expert FFN of a decode step over MXFP4 expert weights (``quantize_experts_mx``'s tensors): x [T, d] bf16,
+    gate logits [T, E], b1 [E, 2f] / b2 [E, d] bf16 -> [T, d] bf16, the chain of ``moe_ffn_mx_reference`` on the plan's
+    val / idx. ``splits``: K splits of the down projection (None: decode_splits_mx). Returns None when the shapes,
+    dtypes or device are not the kernels' (T <= 64, E <= 256, topk <= min(8, E), d % 128 == f % 128 == 0, contiguous
+    operands on the device): the caller keeps its own path."""
+    u8, bf = torch.uint8, torch.bfloat16
+    if x.dim() != 2 or logits.dim() != 2 or w1_q.dim() != 3 or w2_q.dim() != 3 or logits.shape[0] != x.shape[0]:
+        return None
+    (T, d), E, f = x.shape, w1_q.shape[0], w1_q.shape[1] // 2
+    ok = (_decode_plan_ok(logits, topk) and L.has("pa_moe_decode_up_mx") and L.has("pa_mx_quant")
+          and logits.shape[1] == E and d > 0 and f > 0 and d % 128 == 0 and f % 128 == 0
+          and tuple(w1_q.shape) == (E, 2 * f, d // 2) and tuple(w1_s.shape) == (E, 2 * f, d // 32)
+          and tuple(w2_q.shape) == (E, d, f // 2) and tuple(w2_s.shape) == (E, d, f // 32)
+          and (b1 is None or tuple(b1.shape) == (E, 2 * f)) and (b2 is None or tuple(b2.shape) == (E, d))
+          and all(t.dtype == u8 for t in (w1_q, w1_s, w2_q, w2_s))
+          and all(t is None or t.dtype == bf for t in (x, b1, b2))
+          and all(t is None or (t.is_contiguous() and t.device == x.device)
+                  for t in (x, w1_q, w1_s, w2_q, w2_s, b1, b2)))
+    if not ok:
+        return None
+    det = lambda t: None if t is None else t.detach()
+    plan = decode_plan(logits, topk, norm_topk_prob)
+    x_q, x_s = MX.quantize_mx(x, "mxfp8")
+    h_q, h_s = _decode_up_mx(x_q, x_s, w1_q, w1_s, det(b1), plan, topk)
+    return _decode_down_mx(h_q, h_s, w2_q, w2_s, det(b2), plan, topk, splits)

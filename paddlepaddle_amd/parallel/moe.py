@@ -338,7 +338,12 @@ def fused_moe(x, gate_weight, ffn1_weight, ffn2_weight, ffn1_bias=None, ffn1_sca
     (ffn1 [E, d, 2f] -> swiglu -> ffn2 [E, f, d]); routing and both projections run on the device as grouped
     GEMMs over the expert-sorted tokens (no host sync). At most ops.moe.DECODE_DISPATCH_TOKENS tokens with
     nothing to differentiate (decode) run the gate and the FFN in ops.moe.moe_decode_ffn's kernels instead, where
-    their shapes fit."""
+    their shapes fit.
+    ``quant_method="mxfp4"`` (inference only): the experts are MXFP4, ``ffn1_weight`` [E, 2f, d / 2] / ``ffn1_scale``
+    [E, 2f, d / 32] and ``ffn2_weight`` [E, d, f / 2] / ``ffn2_scale`` [E, d, f / 32] as
+    incubate.nn.functional.fused_moe_quantize_mx returns them, activations are mxfp8. Up to
+    ops.moe.DECODE_MAX_TOKENS tokens run ops.moe.moe_decode_ffn_mx's kernels; anything else computes the same chain
+    with ops.moe.moe_ffn_mx_reference and counts in ops.moe.CALLS["mx_fallback"]."""
     from .. import ops as _ops
     from ..ops import moe as M
     xt = x._t
@@ -348,6 +353,22 @@ def fused_moe(x, gate_weight, ffn1_weight, ffn2_weight, ffn1_bias=None, ffn1_sca
     b1 = ffn1_bias._t.reshape(E, -1) if ffn1_bias is not None else None
     b2 = ffn2_bias._t.reshape(E, -1) if ffn2_bias is not None else None
     gl = gate_weight._t.reshape(xf.shape[0], -1)
+    if quant_method == "mxfp4":
+        # the project's own value: ffn*_weight / ffn*_scale are fused_moe_quantize_mx's codes and E8M0 scale bytes
+        w = (ffn1_weight._t, ffn1_scale._t, ffn2_weight._t, ffn2_scale._t)
+        if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (xt, gl, b1, b2)):
+            raise RuntimeError('fused_moe(quant_method="mxfp4") is inference-only (no backward): call it under '
+                               "no_grad() or detach its inputs")
+        out = None
+        if 0 < xf.shape[0] <= M.DECODE_MAX_TOKENS and xf.is_cuda:
+            out = M.moe_decode_ffn_mx(xf.contiguous(), gl, *w, b1, b2, moe_topk, norm_topk_prob)
+        if out is None:  # more tokens, d or f not a multiple of 128, CPU tensors: the same chain in torch
+            M.CALLS["mx_fallback"] += 1
+            val, idx = torch.softmax(gl.float(), -1).topk(moe_topk, -1)
+            if norm_topk_prob:
+                val = val / val.sum(-1, keepdim=True)
+            out = M.moe_ffn_mx_reference(xf.detach(), val, idx, *w, b1, b2).to(xt.dtype)
+        return _wrap(out.reshape(xt.shape))
     if (M.USE_DECODE and 0 < xf.shape[0] <= M.DECODE_DISPATCH_TOKENS and quant_method == "None" and xf.is_cuda
             and not (torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (
                 xt, gl, ffn1_weight._t, ffn2_weight._t, b1, b2)))):

@@ -8,6 +8,13 @@ call by call, median and min-max of the repeats. The stream rate is the bf16 byt
 the gate picked, over the median time. Launches are the device kernels a profiler sees in one eager call.
 
     python tools/bench_moe_decode.py --out profiles/moe_decode_tables.md [--reps 9]
+
+``--mx`` measures the MXFP4 expert FFN instead (fused_moe(quant_method="mxfp4"), the *_mx kernels of moe_decode.hip)
+against the bf16 decode kernels on the same shapes and tokens, alternating with them in the same run; its stream rate
+counts 4.25 bits a weight, and `rel err` is the Frobenius norm of (mxfp4 output - bf16 output) over that of the bf16
+output, the unquantised FFN.
+
+    python tools/bench_moe_decode.py --mx --out profiles/moe_decode_mx_tables.md [--reps 9]
 """
 import argparse
 import statistics
@@ -67,16 +74,76 @@ def launches(fn):
         return None
 
 
+def main_mx(a, flush, head):
+    names = ["decode", "mxfp4", "decode graph", "mxfp4 graph"]
+    lines = ["# MoE decode: MXFP4 expert weights against the bf16 decode kernels", "",
+             head + " `decode`: the bf16 decode kernels. `mxfp4`: fused_moe(quant_method=\"mxfp4\"). `graph`: the same "
+             "call replayed from a hipGraph. `TB/s`: weight bytes of the active experts (bf16: 16 bits a weight, mxfp4: "
+             "4.25) over the median time of the graph replay. `rel err`: Frobenius norm of the difference of the two "
+             "outputs over that of the bf16 output.", "",
+             "| d / f / E / top-k | T | active | splits bf16 / mxfp4 | " + " | ".join(names) +
+             " | mxfp4 graph / decode graph | TB/s decode / mxfp4 | rel err |", "|" + "---|" * 11]
+    for d, f, E, k in SHAPES:
+        w1 = torch.empty(E, d, 2 * f, dtype=torch.bfloat16, device="cuda").normal_(0, d ** -0.5)
+        w2 = torch.empty(E, f, d, dtype=torch.bfloat16, device="cuda").normal_(0, f ** -0.5)
+        w1_q, w1_s, w2_q, w2_s = map(paddle.Tensor, M.quantize_experts_mx(w1, w2))
+        w1, w2 = paddle.Tensor(w1), paddle.Tensor(w2)
+        for T in TOKENS:
+            torch.manual_seed(T)
+            args = (paddle.Tensor(torch.randn(T, d, device="cuda").bfloat16()),
+                    paddle.Tensor(torch.randn(T, E, device="cuda")), w1, w2)
+            mx = lambda: fused_moe(args[0], args[1], w1_q, w2_q, ffn1_scale=w1_s, ffn2_scale=w2_s,
+                                   quant_method="mxfp4", moe_topk=k)
+            n_act = int(M.decode_plan(args[1]._t, k)[6])
+            n0 = L.calls("pa_moe_decode_ffn"), L.calls("pa_moe_decode_up_mx")
+            o_bf, o_mx = call(args, k, True)._t.float(), mx()._t.float()
+            assert L.calls("pa_moe_decode_ffn") == n0[0] + 1 and L.calls("pa_moe_decode_up_mx") == n0[1] + 1
+            err = float((o_mx - o_bf).norm() / o_bf.norm())
+            g_bf = graphed(args, k, True)
+            s = torch.cuda.Stream()
+            s.wait_stream(torch.cuda.current_stream())
+            with torch.cuda.stream(s):
+                mx()
+            torch.cuda.current_stream().wait_stream(s)
+            g_mx = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g_mx):
+                keep = mx()
+            variants = {"decode": (lambda: call(args, k, True), None), "mxfp4": (mx, None),
+                        "decode graph": (g_bf[0].replay, None), "mxfp4 graph": (g_mx.replay, None)}
+            res = interleaved(variants, a.reps, flush, warmup=2)
+            med = {n: statistics.median(res[n]) for n in names}
+            wb = n_act * 3 * d * f
+            ratio = med["mxfp4 graph"] / med["decode graph"]
+            lines.append(f"| {d} / {f} / {E} / {k} | {T} | {n_act} | {M.decode_splits(T * k, E, d, f)} / "
+                         f"{M.decode_splits_mx(T * k, E, d, f)} | " + " | ".join(fmt_ms(res[n]) for n in names)
+                         + (f" | {ratio:.2f}" if ratio <= 1 else f" | **{ratio:.2f}**")
+                         + f" | {wb * 2 / (med['decode graph'] * 1e-3) / 1e12:.2f} / "
+                         f"{wb * 4.25 / 8 / (med['mxfp4 graph'] * 1e-3) / 1e12:.2f} | {err:.4f} |")
+            print(lines[-1], flush=True)
+            with open(a.out, "w") as fh:
+                fh.write("\n".join(lines) + "\n")
+            del g_bf, g_mx, keep
+        del w1, w2, w1_q, w1_s, w2_q, w2_s
+        torch.cuda.empty_cache()
+    print(f"wrote {a.out}")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default="profiles/moe_decode_tables.md")
     ap.add_argument("--reps", type=int, default=9)
     ap.add_argument("--no-launch-count", action="store_true")
+    ap.add_argument("--mx", action="store_true", help="MXFP4 expert weights against the bf16 decode kernels")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_moe_decode needs a HIP device")
     flush = Flusher()
     p = torch.cuda.get_device_properties(0)
+    if a.mx:
+        return main_mx(a, flush, f"Box: {torch.cuda.get_device_name(0)} ({p.gcnArchName}, {p.multi_processor_count} "
+                       f"CUs), torch {torch.__version__}. Date: {time.strftime('%Y-%m-%d')}. Written by "
+                       f"`tools/bench_moe_decode.py --mx --reps {a.reps}`: cold caches, device events, contenders "
+                       f"interleaved; each time is the median of {a.reps} calls in ms with (min-max) behind it.")
     lines = ["# MoE decode: fused_moe on the decode kernels against the grouped path", "",
              f"Box: {torch.cuda.get_device_name(0)} ({p.gcnArchName}, {p.multi_processor_count} CUs), torch "
              f"{torch.__version__}. Date: {time.strftime('%Y-%m-%d')}. Written by `tools/bench_moe_decode.py --reps "
