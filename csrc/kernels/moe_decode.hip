@@ -17,8 +17,8 @@
 //     by side, so bias + silu(value) * gate happens on the accumulators and h [n, f] is written once, in bf16.
 //   * the down projection splits K over gridDim.z into fp32 slabs [split][n][d]; every row of every slab is
 //     written (each sorted row belongs to exactly one expert), so there is no memset and no atomic.
-//   * moe_decode_combine_k sums slabs, bias and the token's experts in a fixed ascending order: bit-identical
-//     from run to run.
+//   * moe_decode_combine_k (moe_combine.h, shared with moe_grouped_mx.hip) sums slabs, bias and the token's experts
+//     in a fixed ascending order: bit-identical from run to run.
 //
 // MXFP4 expert weights (pa_moe_decode_up_mx / pa_moe_decode_down_mx; formats in mx.hip): the same plan and the same
 // combine around two projections built like mx.hip's gemm_mx_small_m_k instead of the LDS ring, since 4.25-bit weights
@@ -38,6 +38,7 @@
 // fragment and keeps LDS out of what limits occupancy (registers do: 2 waves a SIMD up, 3 down).
 #include "launch.h"
 #include "mfma_tile.h"
+#include "moe_combine.h"
 #include "mx_block.h"
 
 namespace pa {
@@ -157,18 +158,6 @@ __global__ __launch_bounds__(256) void moe_decode_plan_k(const TL* __restrict__ 
 }
 
 // ------------------------------------------------------------------------------------------------ FFN
-struct MoeDecArgs {
-  const uint16_t *x, *w1, *w2, *b1, *b2;
-  const float* val;
-  const int *idx, *offs, *perm, *pos, *active, *n_active;
-  uint16_t* h;    // [n, f] bf16, sorted row order
-  float* ws;      // [splits, n, d] fp32
-  uint16_t* out;  // [T, d] bf16
-  int T, E, topk, d, f, n, k_per, splits;
-};
-
-__device__ __forceinline__ float silu(float a) { return a / (1.f + __expf(-a)); }
-
 // One tile of one active expert: C[rows of e (<= MT * 16), 64 columns] over nk K tiles.
 //   UP:  A = x gathered through perm, B = the value and the gate band of w1[e]; epilogue bias + swiglu -> h (bf16)
 //   !UP: A = rows of h,              B = one band of w2[e], K range of split blockIdx.z;   epilogue fp32 slab
@@ -286,32 +275,6 @@ __global__ __launch_bounds__(kMdNW * 64) void moe_decode_down_k(MoeDecArgs p) { 
 template <int MT, bool UP>
 constexpr int moe_decode_smem() {
   return kMdStages * ((MT <= 2 ? 32 : 64) * kMdBK * 2 + (UP ? 2 : 1) * kMdBN * kMdBK * 2);
-}
-
-// out[t][c] = sum_j val[t, j] * (sum_s slab[s][pos[t topk + j]][c] + b2[idx[t, j]][c]), j and s ascending
-__global__ __launch_bounds__(256) void moe_decode_combine_k(MoeDecArgs p) {
-  const int t = blockIdx.y;
-  const int c = (blockIdx.x * 256 + threadIdx.x) * 4;
-  if (c >= p.d) return;
-  float o[4] = {0.f, 0.f, 0.f, 0.f};
-  for (int j = 0; j < p.topk; ++j) {
-    const int ent = t * p.topk + j;
-    const int row = min(max(p.pos[ent], 0), p.n - 1);
-    float4 s = *reinterpret_cast<const float4*>(p.ws + (int64_t)row * p.d + c);
-    for (int sp = 1; sp < p.splits; ++sp) {
-      const float4 u = *reinterpret_cast<const float4*>(p.ws + ((int64_t)sp * p.n + row) * p.d + c);
-      s.x += u.x; s.y += u.y; s.z += u.z; s.w += u.w;
-    }
-    if (p.b2) {
-      float b[4];
-      const int e = min(max(p.idx[ent], 0), p.E - 1);
-      load4_16(p.b2 + (int64_t)e * p.d + c, b);
-      s.x += b[0]; s.y += b[1]; s.z += b[2]; s.w += b[3];
-    }
-    const float w = p.val[ent];
-    o[0] += w * s.x; o[1] += w * s.y; o[2] += w * s.z; o[3] += w * s.w;
-  }
-  *reinterpret_cast<uint2*>(p.out + (int64_t)t * p.d + c) = make_uint2(pack_bf16(o[0], o[1]), pack_bf16(o[2], o[3]));
 }
 
 bool moe_decode_shape_ok(int T, int E, int topk, int d, int f) {

@@ -169,21 +169,6 @@ __device__ __forceinline__ void stage_mx(const uint8_t* __restrict__ g, int ld, 
   }
 }
 
-// Fragment reads of a [R][128 B] image. k_swz(row) has period 16 in row, so the lane's byte offset in fragment row
-// block i is that of block 0 plus 2048 i (an immediate of the ds_read): `lo` is the offset of row (lane & 15), chunk
-// (lane >> 4) ^ k_swz: the fp4 fragment of k-step 0 (k-step 1 is chunk + 4: the offset XOR 64), and the low half of
-// an fp8 fragment, whose high half is chunk + 4 of the same image.
-__device__ __forceinline__ int frag_lo(int lane, int chunk) {
-  const int row = lane & 15;
-  return row * 128 + ((chunk ^ k_swz(row)) << 4);
-}
-__device__ __forceinline__ i32x8 frag4(const char* img, int lo, int s) {
-  return widen(*reinterpret_cast<const uint4*>(img + (lo ^ (64 * s))));
-}
-__device__ __forceinline__ i32x8 frag8(const char* img, int lo) {
-  return join(*reinterpret_cast<const uint4*>(img + lo), *reinterpret_cast<const uint4*>(img + (lo ^ 64)));
-}
-
 template <int FA, int OUT>
 __global__ __launch_bounds__(512, 1) void gemm_mx_kernel(MxArgs p) {
   constexpr int TM = FA == kFmtFp4 ? 256 : 128, TN = 256;

@@ -1,9 +1,11 @@
 // Device pieces of the OCP MX block rule that more than one file needs: the E8M0 byte of a block from its amax, the
-// multiplier that goes with it, the e4m3 conversion, and the operand registers of the block-scaled MFMA. mx.hip
-// holds the formats' description; its quantiser and the MoE decode up projection (moe_decode.hip), which quantises
-// its own output, both build a block from these, so the rule has one source.
+// multiplier that goes with it, the e4m3 conversion, the operand registers of the block-scaled MFMA and the fragment
+// reads of its LDS image. mx.hip holds the formats' description; its quantiser and the MoE up projections
+// (moe_decode.hip, moe_grouped_mx.hip), which quantise their own output, build a block from these, and mx.hip's tiled
+// GEMM and the grouped MoE kernels read the same image, so each rule has one source.
 #pragma once
 #include "common.h"
+#include "mfma_tile.h"
 
 namespace pa {
 
@@ -42,6 +44,21 @@ __device__ __forceinline__ i32x8 widen(uint4 v) {
 __device__ __forceinline__ i32x8 join(uint4 lo, uint4 hi) {
   i32x8 f = {(int)lo.x, (int)lo.y, (int)lo.z, (int)lo.w, (int)hi.x, (int)hi.y, (int)hi.z, (int)hi.w};
   return f;
+}
+
+// Fragment reads of a [R][128 B] image. k_swz(row) has period 16 in row, so the lane's byte offset in fragment row
+// block i is that of block 0 plus 2048 i (an immediate of the ds_read): `lo` is the offset of row (lane & 15), chunk
+// (lane >> 4) ^ k_swz: the fp4 fragment of k-step 0 (k-step 1 is chunk + 4: the offset XOR 64), and the low half of
+// an fp8 fragment, whose high half is chunk + 4 of the same image.
+__device__ __forceinline__ int frag_lo(int lane, int chunk) {
+  const int row = lane & 15;
+  return row * 128 + ((chunk ^ k_swz(row)) << 4);
+}
+__device__ __forceinline__ i32x8 frag4(const char* img, int lo, int s) {
+  return widen(*reinterpret_cast<const uint4*>(img + (lo ^ (64 * s))));
+}
+__device__ __forceinline__ i32x8 frag8(const char* img, int lo) {
+  return join(*reinterpret_cast<const uint4*>(img + lo), *reinterpret_cast<const uint4*>(img + (lo ^ 64)));
 }
 
 }  // namespace pa

@@ -282,6 +282,14 @@ PA_EXPORT int pa_moe_decode_down_mx(const void* hq, const void* hs, const void* 
                                     const int* active, const int* n_active, float* ws, void* out, int T, int E,
                                     int topk, int d, int f, int splits, hipStream_t st);
 
+// moe_grouped_mx.hip
+PA_EXPORT int pa_moe_grouped_up_mx(const void* xq, const void* xs, const void* w1q, const void* w1s, const void* b1,
+                                   const int* offs, const int* perm, void* hq, void* hs, int T, int E, int topk, int d,
+                                   int f, hipStream_t st);
+PA_EXPORT int pa_moe_grouped_down_mx(const void* hq, const void* hs, const void* w2q, const void* w2s, const void* b2,
+                                     const float* val, const int* idx, const int* offs, const int* pos, float* y,
+                                     void* out, int T, int E, int topk, int d, int f, hipStream_t st);
+
 // mx.hip
 PA_EXPORT int pa_mx_quant(const void* x, void* q, void* scales, int64_t R, int64_t K, int in_dtype, int fmt,
                           hipStream_t st);

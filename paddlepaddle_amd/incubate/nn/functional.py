@@ -891,7 +891,9 @@ def fused_moe_quantize_mx(ffn1_weight, ffn2_weight):
     """The expert weights of fused_moe (ffn1 [E, d, 2f], ffn2 [E, f, d]) as MXFP4, K-major per expert: returns
     (w1_q [E, 2f, d / 2], w1_s [E, 2f, d / 32], w2_q [E, d, f / 2], w2_s [E, d, f / 32]), all uint8, which
     ``fused_moe(..., quant_method="mxfp4")`` takes as ffn1_weight, ffn1_scale, ffn2_weight, ffn2_scale. Quantised
-    where the weights are (ops/mx.py holds the rule). Reference: none in Paddle 3.0; the project's own name."""
+    where the weights are (ops/mx.py holds the rule). The same four tensors serve decode (up to 64 tokens,
+    csrc/kernels/moe_decode.hip) and prefill (128 to 65535 tokens, csrc/kernels/moe_grouped_mx.hip); the kernels need
+    d % 128 == f % 128 == 0. Reference: none in Paddle 3.0; the project's own name."""
     from ...ops import moe as _moe
     return tuple(_wrap(t) for t in _moe.quantize_experts_mx(_t(ffn1_weight), _t(ffn2_weight)))
 

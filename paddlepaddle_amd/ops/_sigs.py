@@ -167,6 +167,10 @@ SIGS = {
     "pa_moe_decode_mx_splits": [_i32, _i32, _i32, _i32],
     "pa_moe_decode_up_mx": [_vp] * 11 + [_i32] * 5 + [_vp],
     "pa_moe_decode_down_mx": [_vp] * 13 + [_i32] * 6 + [_vp],
+    # MXFP4 expert FFN past the decode sizes: grouped up (+ SwiGLU + mxfp8) and down (+ combine) projections
+    # (csrc/kernels/moe_grouped_mx.hip)
+    "pa_moe_grouped_up_mx": [_vp] * 9 + [_i32] * 5 + [_vp],
+    "pa_moe_grouped_down_mx": [_vp] * 11 + [_i32] * 5 + [_vp],
     "pa_version": [],
 }
 

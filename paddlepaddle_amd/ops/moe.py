@@ -298,3 +298,70 @@ def moe_decode_ffn_mx(x, logits, w1_q, w1_s, w2_q, w2_s, b1=None, b2=None, topk=
     x_q, x_s = MX.quantize_mx(x, "mxfp8")
     h_q, h_s = _decode_up_mx(x_q, x_s, w1_q, w1_s, det(b1), plan, topk)
     return _decode_down_mx(h_q, h_s, w2_q, w2_s, det(b2), plan, topk, splits)
+
+
+# ------------------------------------------------------------------------------------- prefill, MXFP4 experts
+# csrc/kernels/moe_grouped_mx.hip: the same FFN for any number of tokens as two grouped 128 x 256 block-scaled GEMMs
+# over the expert-sorted rows (pa_moe_grouped_up_mx gathers x_q by token and leaves h as mxfp8, pa_moe_grouped_down_mx
+# ends in the decode path's combine). Gate math in torch on the device, ``route`` for the sort, no host read.
+# fused_moe(quant_method="mxfp4") takes this path from GROUPED_MX_MIN_TOKENS tokens up. The decode kernels end at
+# DECODE_MAX_TOKENS = 64, so 65-127 tokens still run moe_ffn_mx_reference: the existing MX decode test pins a 65-token
+# call to that fallback, and this path is valid for any T >= 1, so a later change can close the gap by lowering the
+# constant to DECODE_MAX_TOKENS + 1 (profiles/moe_prefill_mx.md has the 128-token measurement behind the value).
+GROUPED_MX_MIN_TOKENS = 128
+GROUPED_MX_MAX_TOKENS = 65535
+
+
+def moe_grouped_ffn_mx(x, logits, w1_q, w1_s, w2_q, w2_s, b1=None, b2=None, topk=2, norm_topk_prob=True):
+    """SwiGLU expert FFN over MXFP4 expert weights (``quantize_experts_mx``'s tensors) for any number of tokens:
+    x [T, d] bf16, gate logits [T, E], b1 [E, 2f] / b2 [E, d] bf16 -> [T, d] bf16, the chain of
+    ``moe_ffn_mx_reference`` on val / idx = the top-k of the fp32 softmax (renormalised when ``norm_topk_prob``).
+    Returns None when the shapes, dtypes or device are not the kernels' (1 <= T <= 65535, E <= 256, topk <= min(8, E),
+    d % 128 == f % 128 == 0, d f < 2^31, T topk max(d, f) < 2^36, contiguous operands on the device): the caller keeps
+    its own path."""
+    u8, bf = torch.uint8, torch.bfloat16
+    if x.dim() != 2 or logits.dim() != 2 or w1_q.dim() != 3 or w2_q.dim() != 3 or logits.shape[0] != x.shape[0]:
+        return None
+    (T, d), E, f = x.shape, w1_q.shape[0], w1_q.shape[1] // 2
+    n = T * topk
+    ok = (L.hip_enabled_for(x) and L.has("pa_moe_grouped_up_mx") and L.has("pa_mx_quant") and L.has("pa_moe_route")
+          and 1 <= T <= GROUPED_MX_MAX_TOKENS and 1 <= E <= DECODE_MAX_EXPERTS and 1 <= topk <= min(DECODE_MAX_TOPK, E)
+          and logits.shape[1] == E and d > 0 and f > 0 and d % 128 == 0 and f % 128 == 0
+          and d * f < 2 ** 31 and n * max(d, f) < 2 ** 36
+          and tuple(w1_q.shape) == (E, 2 * f, d // 2) and tuple(w1_s.shape) == (E, 2 * f, d // 32)
+          and tuple(w2_q.shape) == (E, d, f // 2) and tuple(w2_s.shape) == (E, d, f // 32)
+          and (b1 is None or tuple(b1.shape) == (E, 2 * f)) and (b2 is None or tuple(b2.shape) == (E, d))
+          and all(t.dtype == u8 for t in (w1_q, w1_s, w2_q, w2_s))
+          and all(t is None or t.dtype == bf for t in (x, b1, b2))
+          and all(t is None or (t.is_contiguous() and t.device == x.device)
+                  for t in (x, logits, w1_q, w1_s, w2_q, w2_s, b1, b2)))
+    if not ok:
+        return None
+    dev = x.device
+    det = lambda t: None if t is None else t.detach()
+    val, idx = torch.softmax(logits.detach().float(), -1).topk(topk, -1)
+    if norm_topk_prob:
+        val = val / val.sum(-1, keepdim=True)
+    val, idx = val.contiguous(), idx.to(torch.int32).contiguous()
+    offs, perm = route(idx.reshape(-1), E)
+    pos = torch.empty(n, dtype=torch.int32, device=dev)
+    pos[perm] = torch.arange(n, dtype=torch.int32, device=dev)  # the inverse of perm: entry -> sorted row
+    perm = perm.to(torch.int32)
+    x_q, x_s = MX.quantize_mx(x, "mxfp8")
+    h_q = torch.empty(n, f, dtype=u8, device=dev)
+    h_s = torch.empty(n, f // 32, dtype=u8, device=dev)
+    L.call("pa_moe_grouped_up_mx", L.ptr(MX._u8(x_q)), L.ptr(x_s), L.ptr(w1_q), L.ptr(w1_s), L.ptr(det(b1)),
+           L.ptr(offs), L.ptr(perm), L.ptr(h_q), L.ptr(h_s), T, E, topk, d, f, L.stream_ptr())
+    return _grouped_down_mx(h_q, h_s, w2_q, w2_s, det(b2), val, idx, offs, pos)
+
+
+def _grouped_down_mx(h_q, h_s, w2_q, w2_s, b2, val, idx, offs, pos):
+    """Down projection and combine on expert-sorted rows: h_q [n, f] e4m3fn codes / h_s [n, f / 32], val [T, topk]
+    fp32, idx [T, topk] / offs [E + 1] / pos [n] int32 -> out [T, d] bf16 (y [n, d] fp32 of workspace, each row
+    written once)."""
+    (n, f), (E, d), (T, topk) = h_q.shape, w2_q.shape[:2], val.shape
+    y = torch.empty(n, d, dtype=torch.float32, device=h_q.device)
+    out = torch.empty(T, d, dtype=torch.bfloat16, device=h_q.device)
+    L.call("pa_moe_grouped_down_mx", L.ptr(MX._u8(h_q)), L.ptr(h_s), L.ptr(w2_q), L.ptr(w2_s), L.ptr(b2), L.ptr(val),
+           L.ptr(idx), L.ptr(offs), L.ptr(pos), L.ptr(y), L.ptr(out), T, E, topk, d, f, L.stream_ptr())
+    return out

@@ -342,8 +342,10 @@ def fused_moe(x, gate_weight, ffn1_weight, ffn2_weight, ffn1_bias=None, ffn1_sca
     ``quant_method="mxfp4"`` (inference only): the experts are MXFP4, ``ffn1_weight`` [E, 2f, d / 2] / ``ffn1_scale``
     [E, 2f, d / 32] and ``ffn2_weight`` [E, d, f / 2] / ``ffn2_scale`` [E, d, f / 32] as
     incubate.nn.functional.fused_moe_quantize_mx returns them, activations are mxfp8. Up to
-    ops.moe.DECODE_MAX_TOKENS tokens run ops.moe.moe_decode_ffn_mx's kernels; anything else computes the same chain
-    with ops.moe.moe_ffn_mx_reference and counts in ops.moe.CALLS["mx_fallback"]."""
+    ops.moe.DECODE_MAX_TOKENS (64) tokens run ops.moe.moe_decode_ffn_mx's kernels, ops.moe.GROUPED_MX_MIN_TOKENS (128)
+    tokens and more (prefill, up to 65535) run ops.moe.moe_grouped_ffn_mx's grouped kernels; both are hipGraph-safe.
+    Anything else (65-127 tokens, d or f not a multiple of 128, CPU tensors) computes the same chain with
+    ops.moe.moe_ffn_mx_reference, which reads routing on the host, and counts in ops.moe.CALLS["mx_fallback"]."""
     from .. import ops as _ops
     from ..ops import moe as M
     xt = x._t
@@ -362,7 +364,9 @@ def fused_moe(x, gate_weight, ffn1_weight, ffn2_weight, ffn1_bias=None, ffn1_sca
         out = None
         if 0 < xf.shape[0] <= M.DECODE_MAX_TOKENS and xf.is_cuda:
             out = M.moe_decode_ffn_mx(xf.contiguous(), gl, *w, b1, b2, moe_topk, norm_topk_prob)
-        if out is None:  # more tokens, d or f not a multiple of 128, CPU tensors: the same chain in torch
+        elif xf.shape[0] >= M.GROUPED_MX_MIN_TOKENS and xf.is_cuda:
+            out = M.moe_grouped_ffn_mx(xf.contiguous(), gl.contiguous(), *w, b1, b2, moe_topk, norm_topk_prob)
+        if out is None:  # 65-127 tokens, d or f not a multiple of 128, CPU tensors: the same chain in torch
             M.CALLS["mx_fallback"] += 1
             val, idx = torch.softmax(gl.float(), -1).topk(moe_topk, -1)
             if norm_topk_prob:
