@@ -282,6 +282,16 @@ PA_EXPORT int pa_moe_decode_down_mx(const void* hq, const void* hs, const void* 
                                     const int* active, const int* n_active, float* ws, void* out, int T, int E,
                                     int topk, int d, int f, int splits, hipStream_t st);
 
+// moe_decode_wo.hip
+PA_EXPORT int pa_moe_decode_wo_splits(int n, int E, int d, int f, int bits);
+PA_EXPORT int pa_moe_decode_up_wo(const void* x, const void* w1q, const float* w1s, const void* b1, const int* offs,
+                                  const int* perm, const int* active, const int* n_active, void* h, int T, int E,
+                                  int topk, int d, int f, int bits, hipStream_t st);
+PA_EXPORT int pa_moe_decode_down_wo(const void* h, const void* w2q, const float* w2s, const void* b2, const float* val,
+                                    const int* idx, const int* offs, const int* pos, const int* active,
+                                    const int* n_active, float* ws, void* out, int T, int E, int topk, int d, int f,
+                                    int bits, int splits, hipStream_t st);
+
 // moe_grouped_mx.hip
 PA_EXPORT int pa_moe_grouped_up_mx(const void* xq, const void* xs, const void* w1q, const void* w1s, const void* b1,
                                    const int* offs, const int* perm, void* hq, void* hs, int T, int E, int topk, int d,

@@ -898,6 +898,18 @@ def fused_moe_quantize_mx(ffn1_weight, ffn2_weight):
     return tuple(_wrap(t) for t in _moe.quantize_experts_mx(_t(ffn1_weight), _t(ffn2_weight)))
 
 
+def fused_moe_quantize_wo(ffn1_weight, ffn2_weight, algo="weight_only_int8"):
+    """The expert weights of fused_moe (ffn1 [E, d, 2f], ffn2 [E, f, d]) quantised weight-only the reference's way,
+    ``nn.quant.weight_quantize(w[e], algo)`` an expert at a time with per-channel scales: returns (w1_q, w1_s, w2_q,
+    w2_s), which ``fused_moe(..., quant_method=algo)`` takes as ffn1_weight, ffn1_scale, ffn2_weight, ffn2_scale.
+    weight_only_int8: w1_q [E, 2f, d], w2_q [E, d, f] int8; weight_only_int4: w1_q [E, f, d], w2_q [E, d / 2, f]
+    (channels 2j / 2j + 1 in the low / high nibble, stored + 8); scales [E, 2f] / [E, d] fp32. The decode kernels
+    (csrc/kernels/moe_decode_wo.hip) need d % 64 == f % 64 == 0. Reference: none in Paddle 3.0; the project's own
+    name."""
+    from ...ops import moe as _moe
+    return tuple(_wrap(t) for t in _moe.quantize_experts_wo(_t(ffn1_weight), _t(ffn2_weight), algo))
+
+
 def fused_dot_product_attention(query, key, value, attn_mask=None, dropout_p=0.0, is_causal=False, scaling_factor=None,
                                 training=True, name=None):
     o = _ops.flash_attention(_t(query), _t(key), _t(value), causal=is_causal, scale=scaling_factor,

@@ -167,6 +167,10 @@ SIGS = {
     "pa_moe_decode_mx_splits": [_i32, _i32, _i32, _i32],
     "pa_moe_decode_up_mx": [_vp] * 11 + [_i32] * 5 + [_vp],
     "pa_moe_decode_down_mx": [_vp] * 13 + [_i32] * 6 + [_vp],
+    # the same FFN over weight-only int8 / int4 expert weights (csrc/kernels/moe_decode_wo.hip)
+    "pa_moe_decode_wo_splits": [_i32] * 5,
+    "pa_moe_decode_up_wo": [_vp] * 9 + [_i32] * 6 + [_vp],
+    "pa_moe_decode_down_wo": [_vp] * 12 + [_i32] * 7 + [_vp],
     # MXFP4 expert FFN past the decode sizes: grouped up (+ SwiGLU + mxfp8) and down (+ combine) projections
     # (csrc/kernels/moe_grouped_mx.hip)
     "pa_moe_grouped_up_mx": [_vp] * 9 + [_i32] * 5 + [_vp],

@@ -300,6 +300,163 @@ def moe_decode_ffn_mx(x, logits, w1_q, w1_s, w2_q, w2_s, b1=None, b2=None, topk=
     return _decode_down_mx(h_q, h_s, w2_q, w2_s, det(b2), plan, topk, splits)
 
 
+# ------------------------------------------------------------------------------------- weight-only int8 / int4 experts
+# The reference's quant_method="weight_only_int8" / "weight_only_int4": expert weights in nn.quant.weight_quantize's
+# layout, an expert at a time, per-channel scales (group_size = -1). bits 8: w1_q [E, 2f, d], w2_q [E, d, f] int8;
+# bits 4: w1_q [E, f, d], w2_q [E, d / 2, f] (channels 2j / 2j + 1 in the low / high nibble, stored + 8: all 16 codes
+# decode, code 0 is -8); w1_s [E, 2f], w2_s [E, d] fp32. Up to 64 tokens: the plan and the combine of the decode path
+# around csrc/kernels/moe_decode_wo.hip's two projections (four launches, hipGraph-safe). More: ``moe_grouped_ffn_wo``.
+# Inference only.
+CALLS["wo_fallback"] = 0  # fused_moe(quant_method="weight_only_*") calls that ran moe_ffn_wo_reference
+# fused_moe runs the weight-only decode kernels up to this many tokens and dequantise + grouped above
+# (profiles/moe_decode_wo.md)
+WO_DECODE_DISPATCH_TOKENS = DECODE_MAX_TOKENS
+
+
+def quantize_experts_wo(w1, w2, algo="weight_only_int8"):
+    """fused_moe's expert weights w1 [E, d, 2f], w2 [E, f, d] -> (w1_q, w1_s, w2_q, w2_s) in the layout above:
+    ``nn.quant.weight_quantize(w[e], algo)`` stacked over e, the scales as fp32."""
+    from ..nn.quant import weight_quantize
+    if algo not in ("weight_only_int8", "weight_only_int4"):
+        raise ValueError(f"quantize_experts_wo: algo must be weight_only_int8 or weight_only_int4, got {algo!r}")
+    q1, s1 = zip(*((q._t, s._t.float()) for q, s in (weight_quantize(w1[e], algo) for e in range(w1.shape[0]))))
+    q2, s2 = zip(*((q._t, s._t.float()) for q, s in (weight_quantize(w2[e], algo) for e in range(w2.shape[0]))))
+    return torch.stack(q1), torch.stack(s1), torch.stack(q2), torch.stack(s2)
+
+
+def _dequant_wo(q, s, bits, dtype):
+    """One expert's codes [N, K] (bits 4: pair-rows [N / 2, K]) and scales [N] -> [N, K] in ``dtype``."""
+    if bits == 4:
+        u = q.view(torch.uint8)
+        q = torch.stack([u & 0xF, u >> 4], 1).reshape(-1, q.shape[-1]).to(torch.int16) - 8  # rows 2j (low), 2j + 1
+    return q.to(dtype) * s.to(dtype)[:, None]
+
+
+def moe_ffn_wo_reference(x, val, idx, w1_q, w1_s, w2_q, w2_s, b1=None, b2=None, bits=8, dtype=torch.float32):
+    """What the weight-only expert FFN computes, in plain torch with the arithmetic in ``dtype``, for any T, on CPU or
+    device: entry (t, j) with e = idx[t, j] takes u = x[t] . dq(w1_q[e])^T + b1[e], h = silu(value half) * gate half
+    rounded to bf16 (the kernels keep h in bf16), y = h . dq(w2_q[e])^T + b2[e]; out[t] = sum_j val[t, j] y. Returns
+    [T, d] in ``dtype``. The CPU path and the fallback of fused_moe(quant_method="weight_only_int8" | "..._int4")."""
+    T, d = x.shape
+    xd = x.to(dtype)
+    out = torch.zeros(T, d, dtype=dtype, device=x.device)
+    for e in torch.unique(idx).tolist():
+        t, j = torch.nonzero(idx == e, as_tuple=True)
+        u = xd[t] @ _dequant_wo(w1_q[e], w1_s[e], bits, dtype).t()
+        if b1 is not None:
+            u = u + b1[e].to(dtype)
+        a, g = u.chunk(2, -1)
+        y = (torch.nn.functional.silu(a) * g).bfloat16().to(dtype) @ _dequant_wo(w2_q[e], w2_s[e], bits, dtype).t()
+        if b2 is not None:
+            y = y + b2[e].to(dtype)
+        out.index_add_(0, t, val[t, j].to(dtype).unsqueeze(1) * y)
+    return out
+
+
+def decode_splits_wo(n, E, d, f, bits):
+    """K splits the weight-only down projection runs with by default (pa_moe_decode_wo_splits; it counts 64-chunks)."""
+    return int(L.lib().pa_moe_decode_wo_splits(n, E, d, f, bits))
+
+
+def _decode_up_wo(x, w1_q, w1_s, b1, plan, topk, bits):
+    """Up projection + SwiGLU on a ``decode_plan``: x [T, d] bf16 -> h [n, f] bf16 in the plan's sorted row order."""
+    _, _, offs, perm, _, active, n_active = plan
+    (T, d), E, f = x.shape, w1_q.shape[0], w1_s.shape[1] // 2
+    h = torch.empty(T * topk, f, dtype=torch.bfloat16, device=x.device)
+    L.call("pa_moe_decode_up_wo", L.ptr(x), L.ptr(w1_q), L.ptr(w1_s), L.ptr(b1), L.ptr(offs), L.ptr(perm),
+           L.ptr(active), L.ptr(n_active), L.ptr(h), T, E, topk, d, f, bits, L.stream_ptr())
+    return h
+
+
+def _decode_down_wo(h, w2_q, w2_s, b2, plan, topk, bits, splits=None):
+    """Down projection (K = f split ``splits`` ways, None: decode_splits_wo) and combine on a ``decode_plan``:
+    h [n, f] bf16 in sorted row order -> out [T, d] bf16."""
+    val, idx, offs, _, pos, active, n_active = plan
+    (n, f), (E, d) = h.shape, w2_s.shape
+    T, chunks = n // topk, f // 64
+    if splits is None:
+        splits = decode_splits_wo(n, E, d, f, bits)
+    elif not 1 <= splits <= chunks or -(-chunks // (-(-chunks // splits))) != splits:  # ceil(chunks / per) == splits
+        raise ValueError(f"_decode_down_wo: splits ({splits}) must split {chunks} chunks with no empty split")
+    ws = torch.empty(splits, n, d, dtype=torch.float32, device=h.device)
+    out = torch.empty(T, d, dtype=torch.bfloat16, device=h.device)
+    L.call("pa_moe_decode_down_wo", L.ptr(h), L.ptr(w2_q), L.ptr(w2_s), L.ptr(b2), L.ptr(val), L.ptr(idx), L.ptr(offs),
+           L.ptr(pos), L.ptr(active), L.ptr(n_active), L.ptr(ws), L.ptr(out), T, E, topk, d, f, bits, int(splits),
+           L.stream_ptr())
+    return out
+
+
+def _wo_operands_ok(x, logits, w1_q, w1_s, w2_q, w2_s, b1, b2, bits):
+    """The operand checks the weight-only decode and grouped paths share; (E, d, f) or None."""
+    bf = torch.bfloat16
+    if (bits not in (8, 4) or x.dim() != 2 or logits.dim() != 2 or w1_q.dim() != 3 or w2_q.dim() != 3 or w1_s.dim() != 2
+            or logits.shape[0] != x.shape[0]):
+        return None
+    (T, d), (E, f2) = x.shape, w1_s.shape
+    f, pack = f2 // 2, 8 // bits
+    ok = (L.hip_enabled_for(x) and logits.shape[1] == E and d > 0 and f > 0 and d % 64 == 0 and f % 64 == 0
+          and f2 == 2 * f and tuple(w1_q.shape) == (E, 2 * f // pack, d) and tuple(w2_q.shape) == (E, d // pack, f)
+          and tuple(w2_s.shape) == (E, d)
+          and (b1 is None or tuple(b1.shape) == (E, 2 * f)) and (b2 is None or tuple(b2.shape) == (E, d))
+          and all(t.dtype == torch.int8 for t in (w1_q, w2_q)) and all(t.dtype == torch.float32 for t in (w1_s, w2_s))
+          and all(t is None or t.dtype == bf for t in (x, b1, b2))
+          and all(t is None or (t.is_contiguous() and t.device == x.device)
+                  for t in (x, w1_q, w1_s, w2_q, w2_s, b1, b2)))
+    return (E, d, f) if ok else None
+
+
+def moe_decode_ffn_wo(x, logits, w1_q, w1_s, w2_q, w2_s, b1=None, b2=None, topk=2, norm_topk_prob=True, bits=8,
+                      splits=None):
+    """SwiGLU expert FFN of a decode step over weight-only int8 / int4 expert weights (``quantize_experts_wo``'s
+    tensors): x [T, d] bf16, gate logits [T, E], b1 [E, 2f] / b2 [E, d] bf16 -> [T, d] bf16, the chain of
+    ``moe_ffn_wo_reference`` on the plan's val / idx. ``splits``: K splits of the down projection (None:
+    decode_splits_wo). Returns None when the shapes, dtypes or device are not the kernels' (T <= 64, E <= 256,
+    topk <= min(8, E), d % 64 == f % 64 == 0, int8 codes, fp32 scales, contiguous operands on the device): the caller
+    keeps its own path."""
+    if _wo_operands_ok(x, logits, w1_q, w1_s, w2_q, w2_s, b1, b2, bits) is None:
+        return None
+    if not (_decode_plan_ok(logits, topk) and L.has("pa_moe_decode_up_wo")):
+        return None
+    det = lambda t: None if t is None else t.detach()
+    plan = decode_plan(logits, topk, norm_topk_prob)
+    h = _decode_up_wo(x.detach(), w1_q, w1_s, det(b1), plan, topk, bits)
+    return _decode_down_wo(h, w2_q, w2_s, det(b2), plan, topk, bits, splits)
+
+
+def moe_grouped_ffn_wo(x, logits, w1_q, w1_s, w2_q, w2_s, b1=None, b2=None, topk=2, norm_topk_prob=True, bits=8):
+    """The same FFN for any number of tokens with no kernel of its own: both weight stacks are dequantised to bf16 by
+    pa_wo_dequant (an [E, N, K] stack with [E, N] scales is one [E N, K] matrix to it), pa_grouped_gemm multiplies the
+    expert-sorted rows by the [E, N, K] images (its mode 1, which has no bias: the biases are added in torch) with
+    ops.swiglu between the projections, and the token's experts are summed in fp32 in a fixed order. The transient
+    images cost E * 2f * d * 2 bytes for w1 and half that for w2. Returns None when the operands are not the decode
+    kernels' (apart from the token count)."""
+    from . import quant as Q
+    from .activation import swiglu
+    shp = _wo_operands_ok(x, logits, w1_q, w1_s, w2_q, w2_s, b1, b2, bits)
+    if shp is None or not (_hip(x) and L.has("pa_wo_dequant") and 1 <= topk <= logits.shape[1]):
+        return None
+    (E, d, f), T = shp, x.shape[0]
+    n, dev = T * topk, x.device
+    val, idx = torch.softmax(logits.detach().float(), -1).topk(topk, -1)
+    if norm_topk_prob:
+        val = val / val.sum(-1, keepdim=True)
+    offs, perm = route(idx.reshape(-1), E)
+    offs = offs.to(torch.int32).contiguous()
+    pos = torch.empty(n, dtype=torch.long, device=dev)
+    pos[perm] = torch.arange(n, device=dev)  # the inverse of perm: entry -> sorted row
+    eo = expert_of_rows(offs, n).long()
+
+    def project(rows, q, s, N, K, bias):
+        img = Q.dequantize(q.view(-1, K), s.reshape(-1), bits, -1, K, E * N)  # [E N, K] = [E, N, K]
+        y = torch.empty(n, N, dtype=torch.bfloat16, device=dev)
+        _gg(1, rows, img, y, None, offs, E, n, 0, N, K, K, K, N, 0)
+        return y if bias is None else y + bias.detach()[eo]
+
+    u = project(x.detach()[perm // topk].contiguous(), w1_q, w1_s, 2 * f, d, b1)
+    y = project(swiglu(u).contiguous(), w2_q, w2_s, d, f, b2)
+    return (y[pos].float().view(T, topk, d) * val.unsqueeze(-1)).sum(1).to(torch.bfloat16)
+
+
 # ------------------------------------------------------------------------------------- prefill, MXFP4 experts
 # csrc/kernels/moe_grouped_mx.hip: the same FFN for any number of tokens as two grouped 128 x 256 block-scaled GEMMs
 # over the expert-sorted rows (pa_moe_grouped_up_mx gathers x_q by token and leaves h as mxfp8, pa_moe_grouped_down_mx

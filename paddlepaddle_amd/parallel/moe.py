@@ -345,7 +345,16 @@ def fused_moe(x, gate_weight, ffn1_weight, ffn2_weight, ffn1_bias=None, ffn1_sca
     ops.moe.DECODE_MAX_TOKENS (64) tokens run ops.moe.moe_decode_ffn_mx's kernels, ops.moe.GROUPED_MX_MIN_TOKENS (128)
     tokens and more (prefill, up to 65535) run ops.moe.moe_grouped_ffn_mx's grouped kernels; both are hipGraph-safe.
     Anything else (65-127 tokens, d or f not a multiple of 128, CPU tensors) computes the same chain with
-    ops.moe.moe_ffn_mx_reference, which reads routing on the host, and counts in ops.moe.CALLS["mx_fallback"]."""
+    ops.moe.moe_ffn_mx_reference, which reads routing on the host, and counts in ops.moe.CALLS["mx_fallback"].
+    ``quant_method="weight_only_int8"`` / ``"weight_only_int4"`` (inference only): ``ffn*_weight`` / ``ffn*_scale`` are
+    nn.quant.weight_quantize's codes and per-channel scales an expert at a time, as
+    incubate.nn.functional.fused_moe_quantize_wo returns them (int8: [E, 2f, d] / [E, d, f]; int4: [E, f, d] /
+    [E, d / 2, f]; scales [E, 2f] / [E, d], converted to fp32 here when they are not). Up to
+    ops.moe.WO_DECODE_DISPATCH_TOKENS (64) device tokens run ops.moe.moe_decode_ffn_wo's kernels (hipGraph-safe); more
+    run ops.moe.moe_grouped_ffn_wo, which dequantises both stacks to transient bf16 images (E * 2f * d * 2 bytes for
+    ffn1, half that for ffn2) in front of the grouped kernel. CPU tensors and shapes the kernels refuse compute
+    ops.moe.moe_ffn_wo_reference and count in ops.moe.CALLS["wo_fallback"]. Any other ``quant_method`` raises
+    ValueError."""
     from .. import ops as _ops
     from ..ops import moe as M
     xt = x._t
@@ -373,6 +382,28 @@ def fused_moe(x, gate_weight, ffn1_weight, ffn2_weight, ffn1_bias=None, ffn1_sca
                 val = val / val.sum(-1, keepdim=True)
             out = M.moe_ffn_mx_reference(xf.detach(), val, idx, *w, b1, b2).to(xt.dtype)
         return _wrap(out.reshape(xt.shape))
+    if quant_method in ("weight_only_int8", "weight_only_int4"):
+        bits = 8 if quant_method == "weight_only_int8" else 4
+        f32 = lambda t: t if t.dtype == torch.float32 else t.float()
+        w = (ffn1_weight._t, f32(ffn1_scale._t), ffn2_weight._t, f32(ffn2_scale._t))
+        if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (xt, gl, b1, b2)):
+            raise RuntimeError(f'fused_moe(quant_method="{quant_method}") is inference-only (no backward): call it '
+                               "under no_grad() or detach its inputs")
+        out = None
+        if 0 < xf.shape[0] <= M.WO_DECODE_DISPATCH_TOKENS and xf.is_cuda:
+            out = M.moe_decode_ffn_wo(xf.contiguous(), gl, *w, b1, b2, moe_topk, norm_topk_prob, bits)
+        elif xf.shape[0] > M.WO_DECODE_DISPATCH_TOKENS and xf.is_cuda:
+            out = M.moe_grouped_ffn_wo(xf.contiguous(), gl, *w, b1, b2, moe_topk, norm_topk_prob, bits)
+        if out is None:  # CPU tensors, shapes or dtypes the kernels refuse: the same chain in torch
+            M.CALLS["wo_fallback"] += 1
+            val, idx = torch.softmax(gl.float(), -1).topk(moe_topk, -1)
+            if norm_topk_prob:
+                val = val / val.sum(-1, keepdim=True)
+            out = M.moe_ffn_wo_reference(xf.detach(), val, idx, *w, b1, b2, bits).to(xt.dtype)
+        return _wrap(out.reshape(xt.shape))
+    if quant_method != "None":
+        raise ValueError(f'fused_moe: quant_method must be "None", "weight_only_int8", "weight_only_int4" or "mxfp4", '
+                         f"got {quant_method!r}")
     if (M.USE_DECODE and 0 < xf.shape[0] <= M.DECODE_DISPATCH_TOKENS and quant_method == "None" and xf.is_cuda
             and not (torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (
                 xt, gl, ffn1_weight._t, ffn2_weight._t, b1, b2)))):

@@ -15,6 +15,12 @@ counts 4.25 bits a weight, and `rel err` is the Frobenius norm of (mxfp4 output 
 output, the unquantised FFN.
 
     python tools/bench_moe_decode.py --mx --out profiles/moe_decode_mx_tables.md [--reps 9]
+
+``--wo`` does the same for the weight-only int8 / int4 expert FFN (fused_moe(quant_method="weight_only_int8" |
+"weight_only_int4"), csrc/kernels/moe_decode_wo.hip); at 64 tokens it also times the dequantise + grouped path that
+fused_moe takes above ops.moe.WO_DECODE_DISPATCH_TOKENS.
+
+    python tools/bench_moe_decode.py --wo --out profiles/moe_decode_wo_tables.md [--reps 9]
 """
 import argparse
 import statistics
@@ -128,17 +134,105 @@ def main_mx(a, flush, head):
     print(f"wrote {a.out}")
 
 
+def main_wo(a, flush, head):
+    """--wo: the weight-only int8 / int4 decode kernels (csrc/kernels/moe_decode_wo.hip) against the bf16 decode
+    kernels on the unquantised weights, all replayed from hipGraphs and alternating in the same run; at T = 64 also
+    fused_moe's dequantise + grouped path (eager: it allocates its images per call)."""
+    algos = {8: "weight_only_int8", 4: "weight_only_int4"}
+    names = ["bf16 graph", "int8 graph", "int4 graph"]
+    lines = ["# MoE decode: weight-only int8 / int4 expert weights against the bf16 decode kernels", "",
+             head + " `bf16`: the bf16 decode kernels on the unquantised weights. `int8` / `int4`: fused_moe("
+             "quant_method=\"weight_only_int8\" / \"weight_only_int4\") on the decode kernels. All three are replayed "
+             "from a hipGraph. `dq+grouped`: the same call forced onto the dequantise + grouped path, eager, T = 64 "
+             "only. `TB/s`: weight bytes of the active experts (16 / 8 / 4 bits a weight) over the median time. `rel "
+             "err`: Frobenius norm of (quantised output - bf16 output) over that of the bf16 output, Gaussian weights: "
+             "a property of the format. A ratio above 1 (quantised slower than bf16) is bold.", "",
+             "| d / f / E / top-k | T | active | splits bf16 / int8 / int4 | " + " | ".join(names) +
+             " | int8 / bf16 | int4 / bf16 | TB/s bf16 / int8 / int4 | dq+grouped int8 / int4 | rel err int8 / int4 |",
+             "|" + "---|" * 12]
+    for d, f, E, k in SHAPES:
+        w1 = torch.empty(E, d, 2 * f, dtype=torch.bfloat16, device="cuda").normal_(0, d ** -0.5)
+        w2 = torch.empty(E, f, d, dtype=torch.bfloat16, device="cuda").normal_(0, f ** -0.5)
+        wq = {b: tuple(map(paddle.Tensor, M.quantize_experts_wo(w1, w2, algo))) for b, algo in algos.items()}
+        w1, w2 = paddle.Tensor(w1), paddle.Tensor(w2)
+        for T in TOKENS:
+            torch.manual_seed(T)
+            args = (paddle.Tensor(torch.randn(T, d, device="cuda").bfloat16()),
+                    paddle.Tensor(torch.randn(T, E, device="cuda")), w1, w2)
+
+            def wo(b):
+                q = wq[b]
+                return lambda: fused_moe(args[0], args[1], q[0], q[2], ffn1_scale=q[1], ffn2_scale=q[3],
+                                         quant_method=algos[b], moe_topk=k)
+
+            def grouped(b):
+                def run():
+                    keep, M.WO_DECODE_DISPATCH_TOKENS = M.WO_DECODE_DISPATCH_TOKENS, 0
+                    try:
+                        return wo(b)()
+                    finally:
+                        M.WO_DECODE_DISPATCH_TOKENS = keep
+                return run
+
+            n_act = int(M.decode_plan(args[1]._t, k)[6])
+            n0 = L.calls("pa_moe_decode_ffn"), L.calls("pa_moe_decode_up_wo")
+            o_bf = call(args, k, True)._t.float()
+            err = {b: float((wo(b)()._t.float() - o_bf).norm() / o_bf.norm()) for b in algos}
+            assert L.calls("pa_moe_decode_ffn") == n0[0] + 1 and L.calls("pa_moe_decode_up_wo") == n0[1] + 2
+            graphs = {"bf16 graph": graphed(args, k, True)}
+            for b in algos:
+                s = torch.cuda.Stream()
+                s.wait_stream(torch.cuda.current_stream())
+                with torch.cuda.stream(s):
+                    wo(b)()
+                torch.cuda.current_stream().wait_stream(s)
+                g = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(g):
+                    keep = wo(b)()
+                graphs[f"int{b} graph"] = (g, keep)
+            variants = {n: (graphs[n][0].replay, None) for n in names}
+            if T == 64:
+                n1 = L.calls("pa_wo_dequant")
+                variants.update({f"int{b} dq+grouped": (grouped(b), None) for b in algos})
+            res = interleaved(variants, a.reps, flush, warmup=2)
+            assert T != 64 or L.calls("pa_wo_dequant") > n1
+            med = {n: statistics.median(v) for n, v in res.items()}
+            wb = n_act * 3 * d * f
+            bold = lambda r: f"{r:.2f}" if r <= 1 else f"**{r:.2f}**"
+            tb = [wb * bits / 8 / (med[n] * 1e-3) / 1e12 for n, bits in zip(names, (16, 8, 4))]
+            dq = " / ".join(fmt_ms(res[f"int{b} dq+grouped"]) for b in algos) if T == 64 else "-"
+            lines.append(f"| {d} / {f} / {E} / {k} | {T} | {n_act} | {M.decode_splits(T * k, E, d, f)} / "
+                         f"{M.decode_splits_wo(T * k, E, d, f, 8)} / {M.decode_splits_wo(T * k, E, d, f, 4)} | "
+                         + " | ".join(fmt_ms(res[n]) for n in names)
+                         + f" | {bold(med['int8 graph'] / med['bf16 graph'])} | "
+                         f"{bold(med['int4 graph'] / med['bf16 graph'])} | {tb[0]:.2f} / {tb[1]:.2f} / {tb[2]:.2f} | "
+                         f"{dq} | {err[8]:.4f} / {err[4]:.4f} |")
+            print(lines[-1], flush=True)
+            with open(a.out, "w") as fh:
+                fh.write("\n".join(lines) + "\n")
+            del graphs, variants, keep
+        del w1, w2, wq
+        torch.cuda.empty_cache()
+    print(f"wrote {a.out}")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default="profiles/moe_decode_tables.md")
     ap.add_argument("--reps", type=int, default=9)
     ap.add_argument("--no-launch-count", action="store_true")
     ap.add_argument("--mx", action="store_true", help="MXFP4 expert weights against the bf16 decode kernels")
+    ap.add_argument("--wo", action="store_true", help="weight-only int8 / int4 expert weights against the bf16 kernels")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_moe_decode needs a HIP device")
     flush = Flusher()
     p = torch.cuda.get_device_properties(0)
+    if a.wo:
+        return main_wo(a, flush, f"Box: {torch.cuda.get_device_name(0)} ({p.gcnArchName}, {p.multi_processor_count} "
+                       f"CUs), torch {torch.__version__}. Date: {time.strftime('%Y-%m-%d')}. Written by "
+                       f"`tools/bench_moe_decode.py --wo --reps {a.reps}`: cold caches, device events, contenders "
+                       f"interleaved; each time is the median of {a.reps} calls in ms with (min-max) behind it.")
     if a.mx:
         return main_mx(a, flush, f"Box: {torch.cuda.get_device_name(0)} ({p.gcnArchName}, {p.multi_processor_count} "
                        f"CUs), torch {torch.__version__}. Date: {time.strftime('%Y-%m-%d')}. Written by "
