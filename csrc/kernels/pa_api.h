@@ -300,6 +300,14 @@ PA_EXPORT int pa_moe_grouped_down_mx(const void* hq, const void* hs, const void*
                                      const float* val, const int* idx, const int* offs, const int* pos, float* y,
                                      void* out, int T, int E, int topk, int d, int f, hipStream_t st);
 
+// moe_grouped_wo.hip
+PA_EXPORT int pa_moe_grouped_up_wo(const void* x, const void* w1q, const float* w1s, const void* b1, const int* offs,
+                                   const int* perm, void* h, int T, int E, int topk, int d, int f, int bits,
+                                   hipStream_t st);
+PA_EXPORT int pa_moe_grouped_down_wo(const void* h, const void* w2q, const float* w2s, const void* b2,
+                                     const float* val, const int* idx, const int* offs, const int* pos, float* y,
+                                     void* out, int T, int E, int topk, int d, int f, int bits, hipStream_t st);
+
 // mx.hip
 PA_EXPORT int pa_mx_quant(const void* x, void* q, void* scales, int64_t R, int64_t K, int in_dtype, int fmt,
                           hipStream_t st);

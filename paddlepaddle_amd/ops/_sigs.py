@@ -175,6 +175,10 @@ SIGS = {
     # (csrc/kernels/moe_grouped_mx.hip)
     "pa_moe_grouped_up_mx": [_vp] * 9 + [_i32] * 5 + [_vp],
     "pa_moe_grouped_down_mx": [_vp] * 11 + [_i32] * 5 + [_vp],
+    # weight-only int8 / int4 expert FFN past the decode sizes: grouped up (+ SwiGLU) and down (+ combine) projections
+    # that read the codes (csrc/kernels/moe_grouped_wo.hip)
+    "pa_moe_grouped_up_wo": [_vp] * 7 + [_i32] * 6 + [_vp],
+    "pa_moe_grouped_down_wo": [_vp] * 10 + [_i32] * 6 + [_vp],
     "pa_version": [],
 }
 

@@ -308,8 +308,8 @@ def moe_decode_ffn_mx(x, logits, w1_q, w1_s, w2_q, w2_s, b1=None, b2=None, topk=
 # around csrc/kernels/moe_decode_wo.hip's two projections (four launches, hipGraph-safe). More: ``moe_grouped_ffn_wo``.
 # Inference only.
 CALLS["wo_fallback"] = 0  # fused_moe(quant_method="weight_only_*") calls that ran moe_ffn_wo_reference
-# fused_moe runs the weight-only decode kernels up to this many tokens and dequantise + grouped above
-# (profiles/moe_decode_wo.md)
+# fused_moe runs the weight-only decode kernels up to this many tokens, dequantise + grouped above and
+# ``moe_prefill_ffn_wo`` from GROUPED_WO_MIN_TOKENS (profiles/moe_decode_wo.md)
 WO_DECODE_DISPATCH_TOKENS = DECODE_MAX_TOKENS
 
 
@@ -455,6 +455,59 @@ def moe_grouped_ffn_wo(x, logits, w1_q, w1_s, w2_q, w2_s, b1=None, b2=None, topk
     u = project(x.detach()[perm // topk].contiguous(), w1_q, w1_s, 2 * f, d, b1)
     y = project(swiglu(u).contiguous(), w2_q, w2_s, d, f, b2)
     return (y[pos].float().view(T, topk, d) * val.unsqueeze(-1)).sum(1).to(torch.bfloat16)
+
+
+# csrc/kernels/moe_grouped_wo.hip: the same FFN for any number of tokens as two grouped 128 x 256 GEMMs over the
+# expert-sorted rows that read the codes themselves (pa_moe_grouped_up_wo gathers x by token and leaves h in bf16,
+# pa_moe_grouped_down_wo ends in the decode path's combine): no bf16 image of the weights. Gate math in torch on the
+# device, ``route`` for the sort, no host read. fused_moe(quant_method="weight_only_*") takes this path from
+# GROUPED_WO_MIN_TOKENS tokens up. The decode kernels end at 64 tokens, so 65-127 tokens still run moe_grouped_ffn_wo
+# (dequantise + grouped): the existing weight-only decode test pins a 65-token call to pa_wo_dequant == 2 and
+# pa_grouped_gemm == 2, and this path is valid for any T >= 1, so a later change can close the gap by lowering the
+# constant to 65 (profiles/moe_prefill_wo.md has the 128-token measurement behind the value).
+GROUPED_WO_MIN_TOKENS = 128
+GROUPED_WO_MAX_TOKENS = 65535
+
+
+def moe_prefill_ffn_wo(x, logits, w1_q, w1_s, w2_q, w2_s, b1=None, b2=None, topk=2, norm_topk_prob=True, bits=8):
+    """SwiGLU expert FFN over weight-only int8 / int4 expert weights (``quantize_experts_wo``'s tensors) for any number
+    of tokens: x [T, d] bf16, gate logits [T, E], b1 [E, 2f] / b2 [E, d] bf16 -> [T, d] bf16, the chain of
+    ``moe_ffn_wo_reference`` on val / idx = the top-k of the fp32 softmax (renormalised when ``norm_topk_prob``).
+    Returns None when the shapes, dtypes or device are not the kernels' (1 <= T <= 65535, E <= 256, topk <= min(8, E),
+    d % 64 == f % 64 == 0, int8 codes, fp32 scales, contiguous operands on the device): the caller keeps its own
+    path."""
+    shp = _wo_operands_ok(x, logits, w1_q, w1_s, w2_q, w2_s, b1, b2, bits)
+    if shp is None:
+        return None
+    (E, d, f), T = shp, x.shape[0]
+    if not (L.has("pa_moe_grouped_up_wo") and L.has("pa_moe_route") and 1 <= T <= GROUPED_WO_MAX_TOKENS
+            and 1 <= E <= DECODE_MAX_EXPERTS and 1 <= topk <= min(DECODE_MAX_TOPK, E)):
+        return None
+    n, dev = T * topk, x.device
+    det = lambda t: None if t is None else t.detach()
+    val, idx = torch.softmax(logits.detach().float(), -1).topk(topk, -1)
+    if norm_topk_prob:
+        val = val / val.sum(-1, keepdim=True)
+    val, idx = val.contiguous(), idx.to(torch.int32).contiguous()
+    offs, perm = route(idx.reshape(-1), E)
+    pos = torch.empty(n, dtype=torch.int32, device=dev)
+    pos[perm] = torch.arange(n, dtype=torch.int32, device=dev)  # the inverse of perm: entry -> sorted row
+    perm = perm.to(torch.int32)
+    h = torch.empty(n, f, dtype=torch.bfloat16, device=dev)
+    L.call("pa_moe_grouped_up_wo", L.ptr(x.detach()), L.ptr(w1_q), L.ptr(w1_s), L.ptr(det(b1)), L.ptr(offs),
+           L.ptr(perm), L.ptr(h), T, E, topk, d, f, bits, L.stream_ptr())
+    return _prefill_down_wo(h, w2_q, w2_s, det(b2), val, idx, offs, pos, bits)
+
+
+def _prefill_down_wo(h, w2_q, w2_s, b2, val, idx, offs, pos, bits):
+    """Down projection and combine on expert-sorted rows: h [n, f] bf16, val [T, topk] fp32, idx [T, topk] /
+    offs [E + 1] / pos [n] int32 -> out [T, d] bf16 (y [n, d] fp32 of workspace, each row written once)."""
+    (n, f), (E, d), (T, topk) = h.shape, w2_s.shape, val.shape
+    y = torch.empty(n, d, dtype=torch.float32, device=h.device)
+    out = torch.empty(T, d, dtype=torch.bfloat16, device=h.device)
+    L.call("pa_moe_grouped_down_wo", L.ptr(h), L.ptr(w2_q), L.ptr(w2_s), L.ptr(b2), L.ptr(val), L.ptr(idx),
+           L.ptr(offs), L.ptr(pos), L.ptr(y), L.ptr(out), T, E, topk, d, f, bits, L.stream_ptr())
+    return out
 
 
 # ------------------------------------------------------------------------------------- prefill, MXFP4 experts

@@ -350,9 +350,12 @@ def fused_moe(x, gate_weight, ffn1_weight, ffn2_weight, ffn1_bias=None, ffn1_sca
     nn.quant.weight_quantize's codes and per-channel scales an expert at a time, as
     incubate.nn.functional.fused_moe_quantize_wo returns them (int8: [E, 2f, d] / [E, d, f]; int4: [E, f, d] /
     [E, d / 2, f]; scales [E, 2f] / [E, d], converted to fp32 here when they are not). Up to
-    ops.moe.WO_DECODE_DISPATCH_TOKENS (64) device tokens run ops.moe.moe_decode_ffn_wo's kernels (hipGraph-safe); more
-    run ops.moe.moe_grouped_ffn_wo, which dequantises both stacks to transient bf16 images (E * 2f * d * 2 bytes for
-    ffn1, half that for ffn2) in front of the grouped kernel. CPU tensors and shapes the kernels refuse compute
+    ops.moe.WO_DECODE_DISPATCH_TOKENS (64) device tokens run ops.moe.moe_decode_ffn_wo's kernels;
+    ops.moe.GROUPED_WO_MIN_TOKENS (128) tokens and more (prefill, up to 65535) run ops.moe.moe_prefill_ffn_wo's
+    grouped kernels, which read the codes and keep no bf16 copy of the weights; both are hipGraph-safe. In between
+    (65-127 tokens), and where the prefill kernels refuse a call, ops.moe.moe_grouped_ffn_wo dequantises both stacks
+    to transient bf16 images (E * 2f * d * 2 bytes for ffn1, half that for ffn2) in front of the bf16 grouped kernel.
+    CPU tensors and shapes the kernels refuse compute
     ops.moe.moe_ffn_wo_reference and count in ops.moe.CALLS["wo_fallback"]. Any other ``quant_method`` raises
     ValueError."""
     from .. import ops as _ops
@@ -393,7 +396,10 @@ def fused_moe(x, gate_weight, ffn1_weight, ffn2_weight, ffn1_bias=None, ffn1_sca
         if 0 < xf.shape[0] <= M.WO_DECODE_DISPATCH_TOKENS and xf.is_cuda:
             out = M.moe_decode_ffn_wo(xf.contiguous(), gl, *w, b1, b2, moe_topk, norm_topk_prob, bits)
         elif xf.shape[0] > M.WO_DECODE_DISPATCH_TOKENS and xf.is_cuda:
-            out = M.moe_grouped_ffn_wo(xf.contiguous(), gl, *w, b1, b2, moe_topk, norm_topk_prob, bits)
+            if xf.shape[0] >= M.GROUPED_WO_MIN_TOKENS:
+                out = M.moe_prefill_ffn_wo(xf.contiguous(), gl, *w, b1, b2, moe_topk, norm_topk_prob, bits)
+            if out is None:
+                out = M.moe_grouped_ffn_wo(xf.contiguous(), gl, *w, b1, b2, moe_topk, norm_topk_prob, bits)
         if out is None:  # CPU tensors, shapes or dtypes the kernels refuse: the same chain in torch
             M.CALLS["wo_fallback"] += 1
             val, idx = torch.softmax(gl.float(), -1).topk(moe_topk, -1)
