@@ -39,6 +39,7 @@
 #include "launch.h"
 #include "mfma_tile.h"
 #include "moe_combine.h"
+#include "wo_cvt.h"
 
 namespace pa {
 namespace {
@@ -57,34 +58,6 @@ struct MoeGwoArgs {
   float* y;                // down: [n, d] fp32, sorted row order
   int T, E, topk, d, f, n, tiles_n;
 };
-
-// two small integers as a bf16 pair: exact, so the high halves of the floats are the bf16 bits
-__device__ __forceinline__ uint32_t gwo_bf16x2(int a, int b) {
-  return __builtin_amdgcn_perm(__float_as_uint((float)b), __float_as_uint((float)a), 0x07060302u);
-}
-
-// 16 codes along K -> 16 bf16 as the two 16-byte chunks of the image (k 0 .. 7, k 8 .. 15). Per element one signed
-// bit-field extract, one convert and half a byte permute; int4 flips every nibble's top bit first (one XOR a dword),
-// which turns the stored code c = v + 8 into v's 4-bit two's complement. HI: the high nibbles.
-template <int BITS, bool HI>
-__device__ __forceinline__ void gwo_cvt(const uint4& raw, uint4& c0, uint4& c1) {
-  const uint32_t wd[4] = {raw.x, raw.y, raw.z, raw.w};
-  uint32_t o[8];
-#pragma unroll
-  for (int w = 0; w < 4; ++w) {
-    const uint32_t u = BITS == 8 ? wd[w] : wd[w] ^ 0x88888888u;
-    int v[4];
-#pragma unroll
-    for (int b = 0; b < 4; ++b) {
-      const int pos = 8 * b + (BITS == 4 && HI ? 4 : 0);
-      v[b] = (int)(u << (32 - BITS - pos)) >> (32 - BITS);
-    }
-    o[2 * w] = gwo_bf16x2(v[0], v[1]);
-    o[2 * w + 1] = gwo_bf16x2(v[2], v[3]);
-  }
-  c0 = make_uint4(o[0], o[1], o[2], o[3]);
-  c1 = make_uint4(o[4], o[5], o[6], o[7]);
-}
 
 // One 128 x 256 tile of one expert. UP: A = x gathered through perm, B = value + gate channels of w1_q[e], epilogue
 // scale + bias + SwiGLU -> h. !UP: A = sorted rows of h, B = w2_q[e], epilogue scale -> y.

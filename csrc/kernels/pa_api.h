@@ -371,3 +371,9 @@ PA_EXPORT int pa_wo_gemm(const void* x, const void* xo, const float* sx, const v
                          int group, int splits, hipStream_t st);
 PA_EXPORT int pa_wo_dequant(const void* w, const float* scale, void* out, int N, int K, int bits, int group,
                             hipStream_t st);
+
+// wo_gemm_prefill.hip
+PA_EXPORT int pa_wo_gemm_prefill_plan(int64_t M, int64_t N, int64_t K, int* tile_m, int* splits);
+PA_EXPORT int pa_wo_gemm_prefill(const void* x, const void* w, const float* scale, const void* bias, void* y,
+                                 float* ws, int M, int N, int K, int ldx, int ldy, int bits, int group, int tile_m,
+                                 int splits, hipStream_t st);

@@ -106,6 +106,9 @@ SIGS = {
     "pa_wo_gemm": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp],
     "pa_wo_gemm_splits": [_i64, _i64, _i64, _i32],
     "pa_wo_dequant": [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp],
+    # weight-only int8 / int4 GEMM past the decode sizes, on the codes (csrc/kernels/wo_gemm_prefill.hip)
+    "pa_wo_gemm_prefill_plan": [_i64, _i64, _i64, _vp, _vp],
+    "pa_wo_gemm_prefill": [_vp] * 6 + [_i32] * 9 + [_vp],
     # MX (block-scaled fp4 / fp8) quantiser and GEMMs (csrc/kernels/mx.hip)
     "pa_mx_quant": [_vp, _vp, _vp, _i64, _i64, _i32, _i32, _vp],
     "pa_gemm_mx": [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i32, _i32, _vp],

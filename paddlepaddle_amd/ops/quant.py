@@ -7,8 +7,11 @@ int4 pairs [N/2, K] (channels 2j / 2j+1 in the low / high nibble, stored +8), sc
 Decode shapes (M <= 64 rows) run ``pa_wo_gemm`` — the weight bytes stream once and are dequantised in registers in
 front of the MFMA — or the bf16 small-M GEMM on a cached dequantised image, whichever the per-shape timing
 (ops.gemm.choose, key "wo_linear") finds faster: the decode kernel wins where the weight stream dominates, the bf16
-GEMM where the activation rows make the product compute-bound (profiles/weight_only_gemm_r4.log). Longer inputs
-run the bf16 MFMA GEMM on the cached image. The image cache (``dequantized``) is bounded by
+GEMM where the activation rows make the product compute-bound (profiles/weight_only_gemm_r4.log). From
+WO_PREFILL_MIN_M rows (N % 64 == 0) ``pa_wo_gemm_prefill`` (csrc/kernels/wo_gemm_prefill.hip) reads the codes
+as well: with the image cache off or too small for the image no image is built at all, otherwise the per-shape
+timing (key "wo_prefill") decides between it and the bf16 GEMM on the cached image (profiles/wo_prefill.md). The
+rows in between, and N % 64 != 0, run the bf16 MFMA GEMM on the image. The image cache (``dequantized``) is bounded by
 FLAGS_weight_only_dequant_cache_mb (0: no cache — every long call dequantises, decode always streams the quantised
 weight) and keyed by the weight / scale storage and version, so an updated weight is re-dequantised.
 LLM.int8 above the decode shapes (``llm_int8_gemm``) also runs on the MFMA GEMM: the inlier columns enter as the
@@ -17,6 +20,7 @@ row / channel scales applied to the fp32 result.
 """
 from __future__ import annotations
 
+import ctypes
 from collections import OrderedDict
 
 import torch
@@ -24,6 +28,7 @@ import torch
 from . import _loader as L
 
 DECODE_MAX_M = 64
+WO_PREFILL_MIN_M = 256
 
 
 def _scale_f32(scale):
@@ -77,6 +82,24 @@ def _bf16_linear(x2, wd, b):
     return _fwd_mm(x2, wd.t(), b)
 
 
+def wo_prefill(x2, w, sc, b, bits, group, tile_m=None, splits=None):
+    """y[M, N] bf16 = x2[M, K] . dequant(w)^T (+ b) on pa_wo_gemm_prefill, which reads the codes: x2 bf16 contiguous,
+    sc fp32 contiguous, b bf16 or None. ``tile_m`` (128 / 256) and ``splits`` (a divisor of K / 64) default to the
+    launcher's plan."""
+    M, K = x2.shape
+    N = w.shape[0] * (2 if bits == 4 else 1)
+    if tile_m is None or splits is None:
+        plan = (ctypes.c_int * 2)()
+        if L.lib().pa_wo_gemm_prefill_plan(M, N, K, ctypes.byref(plan, 0), ctypes.byref(plan, 4)):
+            raise ValueError(f"weight-only prefill GEMM needs K % 64 == 0 and N % 64 == 0 (K={K}, N={N})")
+        tile_m, splits = tile_m or plan[0], splits or plan[1]
+    y = torch.empty(M, N, dtype=torch.bfloat16, device=x2.device)
+    ws = torch.empty(splits * M * N, dtype=torch.float32, device=x2.device) if splits > 1 else None
+    L.call("pa_wo_gemm_prefill", L.ptr(x2), L.ptr(w), L.ptr(sc), L.ptr(b), L.ptr(y), L.ptr(ws), M, N, K, K, N, bits,
+           group, tile_m, splits, L.stream_ptr())
+    return y
+
+
 def wo_linear(x, w, scale, bias, bits, group, llm=None):
     """y[..., N] = x[..., K] . dequant(w)^T (+ bias) for bf16 ``x``; ``llm`` = (xq, xo, sx) switches the decode
     kernel to LLM.int8 (x is then ignored)."""
@@ -123,6 +146,15 @@ def wo_linear(x, w, scale, bias, bits, group, llm=None):
         return llm_int8_gemm(None, w, scale, b, llm=llm).reshape(*x.shape[:-1], N)
     x2 = x2.to(torch.bfloat16).contiguous()
     wd = dequantized(w, scale, bits, group, K, N)
+    if M >= WO_PREFILL_MIN_M and N % 64 == 0:
+        w = w.contiguous()
+        if wd is not None:
+            from . import gemm as G
+            key = ("wo_prefill", 1 << (M - 1).bit_length(), N, K, bits, group)
+            cand = {"wo": lambda: wo_prefill(x2, w, sc, b, bits, group), "bf16": lambda: _bf16_linear(x2, wd, b)}
+            if G.choose(key, cand, cold=True) == "bf16":
+                return cand["bf16"]().reshape(*x.shape[:-1], N)
+        return wo_prefill(x2, w, sc, b, bits, group).reshape(*x.shape[:-1], N)
     if wd is None:
         wd = dequantize(w, scale, bits, group, K, N)        # [N, K]: B K-major
     return _bf16_linear(x2, wd, b).reshape(*x.shape[:-1], N)

@@ -36,7 +36,7 @@ HIP_FLAGS = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-munsafe-f
 _NO_PK_F32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 HIP_FILE_FLAGS = {"prefill_paged_attn.hip": _NO_PK_F32, "mx.hip": _NO_PK_F32,
                   "moe_decode.hip": _NO_PK_F32, "moe_grouped_mx.hip": _NO_PK_F32, "moe_decode_wo.hip": _NO_PK_F32,
-                  "moe_grouped_wo.hip": _NO_PK_F32}
+                  "moe_grouped_wo.hip": _NO_PK_F32, "wo_gemm_prefill.hip": _NO_PK_F32}
 
 
 def _newer(src_list, out):
